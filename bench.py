@@ -7,7 +7,11 @@ frame of synthetic input per rank: 512x512 rays x (64 coarse + 48 fine) MLP quer
 frames are independent, so N ranks render N frames per step with no data-path collective ("weak" scaling).
 Rank 0 prints ONE JSON line (the last line of stdout).
 
-What the default run (N = 1) times, each as its own loop of W warm-up + K timed steps between synchronisations:
+A plain run times the headline and nothing else: set-up, W warm-up steps, K timed steps of cfg2 in the library's default arithmetic
+mode (or the one HAVATAR_MLP names), the result line.  `--dump-outputs DIR` then writes what the last timed step returned as
+DIR/<name>.npy (write_outputs), the same inputs in every run with the same arguments.
+
+What `--full` (N = 1) times in addition, each as its own loop of W warm-up + K timed steps between synchronisations:
   * cfg2 in every arithmetic mode of the radiance MLP -- bf16x3 (every operand hi + mid + lo bf16 = 24 bits, six products), exact fp32
     MFMA, and the 22-bit fp16 double split.  `value` is the FASTEST MODE THAT IS NOT NARROWER THAN THE REFERENCE'S fp32; the fp16
     double split is reported under modes.fp16x2 and is never the headline.
@@ -17,6 +21,8 @@ What the default run (N = 1) times, each as its own loop of W warm-up + K timed 
     tri-plane encoders.
   * roofline.power: socket power and shader clock sampled during a sustained replay of the headline loop (the kernel runs at the
     socket power cap, docs/history/DESIGN_r1-r4.md 3.13).
+  * config.phase_ms and the rest of roofline: per-phase HIP-event times, the live rocprofv3 traffic passes, the committed counters.
+With --full, cfg3 at N = 1 also tries B = 1 / 2 / 4 frames per replay, cfg4 times the upsampler alone and cfg5 the MLP kernels.
 
 Other workloads (not what the driver runs; same JSON contract):
   --workload cfg3 [--frames 64]   BASELINE configs[2]: a batch of 64 frames dealt round-robin to the ranks (8 per GPU on 8 GPUs), finished
@@ -73,6 +79,10 @@ EXEC_INSTR_PER_TILE = {"fp16x2": 132, "bf16x3": 264, "f32": 352, "fp16x2+mx": 16
 PARK_FLOP_PER_TILE = 48 * 32768
 CFG3_NOTE = ("cfg3: one step = a batch of %d frames dealt round-robin to %d rank(s) (%d per rank); each frame is the cfg2 workload below; the "
              "finished RGB frame of round r ([3,512,512] fp32 = 3.1 MB per rank) is all-gathered over RCCL while round r+1 renders")
+# --dump-outputs: names of what one step of each workload returns, and the bytes of array data written in all (the .npy headers stay
+# well inside 64 MB)
+OUT_NAMES = {"cfg2": ("render", "mask", "latent_code_loss"), "cfg3": ("frames",), "cfg4": ("image",), "cfg5": ("loss", "parts", "psnr")}
+DUMP_BYTES = 60 * 10 ** 6
 
 
 def emit_line(obj):
@@ -85,6 +95,43 @@ def emit_line(obj):
     except Exception:
         pass
     print(json.dumps(obj), flush=True)
+
+
+def output_arrays(out, names=()):
+    """What a step returned -- a tensor, a number, or a tuple / list / dict of them; None is skipped -- as {name: host ndarray}: float64
+    stays float64, every other type becomes float32.  names[i] names element i of a tuple; nested names are joined by '.'."""
+    import numpy as np
+    import torch
+    if isinstance(out, dict):
+        items = [(str(k), v) for k, v in out.items()]
+    elif isinstance(out, (tuple, list)):
+        items = [(names[i] if i < len(names) else str(i), v) for i, v in enumerate(out)]
+    else:
+        items = [(names[0] if names else "out", out)]
+    arrs = {}
+    for name, v in items:
+        if v is None:
+            continue
+        if isinstance(v, (dict, tuple, list)):
+            arrs.update({name + "." + k: a for k, a in output_arrays(v).items()})
+        elif torch.is_tensor(v):
+            v = v.detach().cpu()
+            arrs[name] = np.array((v if v.dtype == torch.float64 else v.float()).numpy(), order="C")          # (a copy: never a view of a live buffer)
+        else:
+            arrs[name] = np.asarray(v, np.float64)
+    return arrs
+
+
+def write_outputs(d, arrs):
+    """DIR/<name>.npy for every array, DUMP_BYTES of data in all: an array larger than its share is written as a fixed sample of its
+    flattened elements (sorted indices drawn by numpy's default_rng(0)), the same elements in every run."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_BYTES // max(len(arrs), 1)
+    for name, a in arrs.items():
+        if a.nbytes > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))]
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def cpu_model():
@@ -318,15 +365,14 @@ def run_cfg5(args, emit=True):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = runner(inp, target, mask)[0]
+        last = runner(inp, target, mask)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.steps
+    loss = last[0]
+    if emit and args.dump_outputs:
+        write_outputs(args.dump_outputs, output_arrays(last, OUT_NAMES["cfg5"]))
     rays = inp["ray_batch"].shape[0] * inp["ray_batch"].shape[1]
     queries = rays * Q_PER_RAY
-    from havatar_amd.native import mlp_train
-    info = mlp_train.bench_kernels(trainer.model_coarse, queries, dev)          # HIP events around the MLP kernels alone, same shapes
-    flop = 3 * FLOP_PER_QUERY * queries                                        # forward + (data + weight) gradients = 3x forward
-    kern_s = info["fwd_ms"] * 1e-3 + info["bwd_ms"] * 1e-3
     res = {"metric": "train_avatar.py optimisation steps/s (2 x 4096 rays x 64+48 samples, fwd + bwd + Adam)", "value": round(1.0 / dt, 3),
            "unit": "steps/s", "n_gpus": 1, "steps": args.steps, "warmup": max(args.warmup, 4), "ms_per_step": round(1e3 * dt, 3),
            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -334,16 +380,22 @@ def run_cfg5(args, emit=True):
            "data": "synthetic",
            "config": {"workload": "cfg5: Trainer.forward(mode=train) + loss (train_avatar.py:121-146 without LPIPS) + backward + Adam, "
                                   "B=2 x 4096 rays, perturb on, radiance_field_noise_std 0.1", "rays": rays, "queries": queries,
-                      "hipgraph": use_graph, "loss": round(float(loss), 6), "mlp_mode": info["mode"],
-                      "phase_ms": {"mlp_forward_2_passes": round(info["fwd_ms"], 3), "mlp_backward_2_passes": round(info["bwd_ms"], 3)}},
-           "roofline": {"bound": "mfma", "achieved": round(flop / kern_s / 1e12, 2), "peak": PEAK_BF16_MFMA / 1e12, "unit": "TFLOP/s",
-                        "frac": round(flop / kern_s / PEAK_BF16_MFMA, 4), "traffic": None, "flop_per_step": flop,
-                        "hbm_algorithmic_bytes": info["bytes"], "hbm_achieved_GBps": round(info["bytes"] / kern_s / 1e9, 1),
-                        "hbm_frac_of_8TBps": round(info["bytes"] / kern_s / 8e12, 4),
-                        "note": "the dominant kernels of the path under training = the radiance MLP forward + backward (hav_mlp_fwd / "
-                                "hav_mlp_bwd_data / hav_mlp_bwd_weights); achieved = 3 x 94848 FLOP x queries / their summed time; at 917 504 "
-                                "queries the contraction is small (261 GFLOP) and the kernels stream X / dX / activations: both fractions "
-                                "are reported"}}
+                      "hipgraph": use_graph, "loss": round(float(loss), 6)}}
+    if args.full:
+        from havatar_amd.native import mlp_train
+        info = mlp_train.bench_kernels(trainer.model_coarse, queries, dev)          # HIP events around the MLP kernels alone, same shapes
+        flop = 3 * FLOP_PER_QUERY * queries                                        # forward + (data + weight) gradients = 3x forward
+        kern_s = info["fwd_ms"] * 1e-3 + info["bwd_ms"] * 1e-3
+        res["config"].update(mlp_mode=info["mode"],
+                             phase_ms={"mlp_forward_2_passes": round(info["fwd_ms"], 3), "mlp_backward_2_passes": round(info["bwd_ms"], 3)})
+        res["roofline"] = {"bound": "mfma", "achieved": round(flop / kern_s / 1e12, 2), "peak": PEAK_BF16_MFMA / 1e12, "unit": "TFLOP/s",
+                           "frac": round(flop / kern_s / PEAK_BF16_MFMA, 4), "traffic": None, "flop_per_step": flop,
+                           "hbm_algorithmic_bytes": info["bytes"], "hbm_achieved_GBps": round(info["bytes"] / kern_s / 1e9, 1),
+                           "hbm_frac_of_8TBps": round(info["bytes"] / kern_s / 8e12, 4),
+                           "note": "the dominant kernels of the path under training = the radiance MLP forward + backward (hav_mlp_fwd / "
+                                   "hav_mlp_bwd_data / hav_mlp_bwd_weights); achieved = 3 x 94848 FLOP x queries / their summed time; at 917 504 "
+                                   "queries the contraction is small (261 GFLOP) and the kernels stream X / dX / activations: both fractions "
+                                   "are reported"}
     if emit:
         emit_line(res)
     return res
@@ -377,17 +429,23 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: every arithmetic mode, per-phase kernel times, roofline, extra.*, "
+                         "the CPU baseline (the options below marked --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step returned as DIR/<name>.npy "
+                                                          "(float32 / float64, a fixed sample of an array beyond its share of 60 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-rows", type=int, default=0, help="image rows timed on the CPU (0 = auto: the whole frame if it fits ~25 s)")
     ap.add_argument("--perturb", type=int, default=1, help="stratified jitter on (reference default for inference)")
     ap.add_argument("--graph", type=int, default=1, help="replay the frame as one hipGraph (0 = eager launches)")
-    ap.add_argument("--live-pmc", type=int, default=1, help="measure roofline.traffic in this run (2 rocprofv3 --pmc passes, ~1 min; N=1 only)")
+    ap.add_argument("--live-pmc", type=int, default=1,
+                    help="--full: measure roofline.traffic in this run (2 rocprofv3 --pmc passes, ~1 min; N=1 only)")
     ap.add_argument("--workload", choices=["cfg2", "cfg3", "cfg4", "cfg5"], default="cfg2")
-    ap.add_argument("--extras", type=int, default=1, help="N = 1, cfg2: also time every arithmetic mode, cfg4 and cfg5 (extra.*) in this run")
+    ap.add_argument("--extras", type=int, default=1, help="--full, N = 1, cfg2: also time every arithmetic mode, cfg4 and cfg5 (extra.*) in this run")
     ap.add_argument("--frames", type=int, default=64, help="cfg3: frames per batch (one step = one batch)")
     ap.add_argument("--frame-batch", type=int, default=0,
-                    help="cfg3: frames per hipGraph replay (the encoders see a batch, the march B x R rays in one launch).  0 = at N = 1 time "
-                         "B = 1, 2 and 4 and report the fastest (config.frames_per_replay holds all three); at N > 1: 4")
+                    help="cfg3: frames per hipGraph replay (the encoders see a batch, the march B x R rays in one launch).  0 = 4 (1 in CPU plumbing mode); with --full "
+                         "at N = 1 time B = 1, 2 and 4 and report the fastest (config.frames_per_replay holds all three)")
     ap.add_argument("--force-collective", type=int, default=0,
                     help="cfg3 at N=1: create a 1-rank RCCL group and send every finished frame through the side-stream all_gather "
                          "(the exchange step's HIP branch on one GPU)")
@@ -516,7 +574,7 @@ def main():
 
     # ---- which arithmetic mode(s) ------------------------------------------------------------------------------------
     env_mode = MODE_OF_ENV.get(os.environ.get("HAVATAR_MLP", ""), None)
-    all_modes = (not cpu) and world == 1 and args.workload == "cfg2" and bool(args.extras) and env_mode is None
+    all_modes = (not cpu) and world == 1 and args.workload == "cfg2" and args.full and bool(args.extras) and env_mode is None
     if cpu:
         mode_list = ["f32"]
     elif all_modes:
@@ -532,6 +590,10 @@ def main():
     def set_mode(mode):
         if m is not None:
             m.mlp_mode = MLP_CONST[mode]
+
+    def snapshot(out):
+        """--dump-outputs: the host copy of a loop's last step, taken before anything else runs on the same buffers."""
+        return output_arrays(out, OUT_NAMES[args.workload]) if (args.dump_outputs and rank == 0) else None
 
     upsample = None
     gather = None
@@ -568,7 +630,7 @@ def main():
                             r += 1
                     return gather.finalize()
                 return step
-            fbs = [args.frame_batch] if args.frame_batch > 0 else ([1, 2, 4] if (world == 1 and not cpu) else [1 if cpu else 4])
+            fbs = [args.frame_batch] if args.frame_batch > 0 else ([1, 2, 4] if (world == 1 and not cpu and args.full) else [1 if cpu else 4])
             frames_per_step = args.frames
             frames_per_replay = {}
             best = None
@@ -577,10 +639,10 @@ def main():
                 dt_, fps_, out_ = timed_loop(st, frames_per_step)
                 frames_per_replay[str(fb)] = {"frames_per_s": round(fps_, 3), "ms_per_frame": round(1e3 * dt_ / (args.steps * args.frames) * world, 3)}
                 if best is None or fps_ > best[1]:
-                    best = (dt_, fps_, out_, st, fb)
+                    best = (dt_, fps_, out_, st, fb, snapshot(out_))          # (every B's loop returns the same gather buffer)
             dt, fps, out, step = best[:4]
             frames_per_replay["used"] = best[4]
-            loops[mode] = {"dt": dt, "fps": fps, "render": render, "step": step, "frames_per_step": frames_per_step}
+            loops[mode] = {"dt": dt, "fps": fps, "render": render, "step": step, "frames_per_step": frames_per_step, "outputs": best[5]}
             continue
         elif args.workload == "cfg4":
             upsample = make_upsampler(args, render, poses, dev)
@@ -593,7 +655,14 @@ def main():
                 return render(poses[i % len(poses)])
             frames_per_step = world
         dt, fps, out = timed_loop(step, frames_per_step)
-        loops[mode] = {"dt": dt, "fps": fps, "render": render, "step": step, "frames_per_step": frames_per_step}
+        loops[mode] = {"dt": dt, "fps": fps, "render": render, "step": step, "frames_per_step": frames_per_step, "outputs": snapshot(out)}
+
+    # ---- the headline: the fastest timed mode that is NOT narrower than the reference's fp32 --------------------------------
+    wide = [k for k in loops if MODES[k][2]]
+    head = max(wide, key=lambda k: loops[k]["fps"]) if wide else mode_list[0]
+    dt, fps, frames_per_step = loops[head]["dt"], loops[head]["fps"], loops[head]["frames_per_step"]
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, loops[head]["outputs"])
 
     if cpu:
         # plumbing mode: no kernels to profile; report the contract fields and what the collective moved
@@ -610,10 +679,37 @@ def main():
             dist.destroy_process_group()
         return
 
-    # ---- the headline: the fastest timed mode that is NOT narrower than the reference's fp32 --------------------------------
-    wide = [k for k in loops if MODES[k][2]]
-    head = max(wide, key=lambda k: loops[k]["fps"]) if wide else mode_list[0]
-    dt, fps, frames_per_step = loops[head]["dt"], loops[head]["fps"], loops[head]["frames_per_step"]
+    res = {
+        "metric": ("stage-two HD frames/sec: 512^2 NeRF volume render (64 samples/ray) + SWGAN_unet upsampler to 1024^2" if args.workload == "cfg4"
+                   else "rendered frames/sec @512^2, 64 samples/ray"), "value": round(fps, 3), "unit": "frames/s",
+        "n_gpus": world, "rccl_ranks_seen": ranks_seen, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 3),
+        "higher_is_better": True, "scaling": "strong" if args.workload == "cfg3" else "weak", "vs_baseline": None, "dtype": DTYPE[head],
+        "data": "synthetic",
+        "config": {"batch": CFG3_NOTE % (args.frames, world, -(-args.frames // world)) if args.workload == "cfg3" else None,
+                   "workload": "cfg2: Trainer.forward(render_full_img=True) for one 512x512 frame per GPU per step: tri-plane encoders "
+                               "(P3: 2x StyleGAN_zxc: 3x3 / up-sampling convolutions on split-fp16 MFMA HIP kernels with the block glue fused, stride-2 and 1x1 ones on MIOpen, HIP upfirdn2d/fused_bias_act) -> per-frame plane projection -> fused "
+                               "ray march (P5-P12) over 262144 rays x (64 coarse + 48 fine) = 29.36M radiance-MLP queries -> [1,67,512,512]",
+                   "arithmetic_mode": head, "operand_bits": MODES[head][1],
+                   "headline_rule": "value = the fastest TIMED mode whose operands are not narrower than the reference's fp32 (a plain run times one "
+                                    "mode; --full times every mode, modes.*)",
+                   "stage_two": ({"output": [1, 3, 2 * H, 2 * W],
+                                  "what": "BASELINE configs[3]: the step is the cfg2 frame below followed by SWGAN_unet(512 -> 1024) on render[:, 3:] "
+                                          "(avatarHD_reenactment.py:153-160): its 3x3 / up-sampling convolutions, Haar transforms, upfirdn2d and "
+                                          "fused_bias_act are kernels of this library, stride-2 / 1x1 convolutions MIOpen; phase_ms.encoders_P3_inside_the_graph "
+                                          "includes the upsampler in this workload"} if args.workload == "cfg4" else None),
+                   "rays_per_frame": H * W, "num_coarse": S_C, "num_fine": S_F, "perturb": perturb, "hipgraph": bool(args.graph), "frames_per_replay": frames_per_replay,
+                   "hipgraph_packet_capture": hipgraph_state(),          # in_force = the variable was 0 before this process's first HIP call (ROCm graph-replay fault, havatar_amd/__init__.py)
+                   "parallelism": ("frames sharded, %d rank(s), one overlapped all_gather of finished frames per round" if args.workload == "cfg3"
+                                   else "frames sharded, %d rank(s), no data-path collective") % world,
+                   "exchange": (("RCCL all_gather_into_tensor from a side stream, %d-rank group%s" % (world, " (forced at N = 1)" if world == 1 else ""))
+                                if (args.workload == "cfg3" and gather is not None and gather.collective) else None)}}
+    if not args.full:          # a plain run: the headline loop is all it measures
+        if dist.is_initialized():
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            emit_line(res)
+        return
 
     # ---- outside the timed region: per-phase device times (HIP events on the launch stream = torch's current stream) ----
     def timed(fn, n):
@@ -743,37 +839,17 @@ def main():
                 cfg4_ms = timed(lambda: upsample(feat), n_ev)
         step_ms = 1e3 * dt / args.steps / (frames_per_step / world)               # per frame of this rank
         power_bound = bool(power and power.get("sclk_GHz") and power["sclk_GHz"] < 2.3)
-        res = {
-            "metric": ("stage-two HD frames/sec: 512^2 NeRF volume render (64 samples/ray) + SWGAN_unet upsampler to 1024^2" if args.workload == "cfg4"
-                       else "rendered frames/sec @512^2, 64 samples/ray"), "value": round(fps, 3), "unit": "frames/s",
-            "n_gpus": world, "rccl_ranks_seen": ranks_seen, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 3),
-            "higher_is_better": True, "scaling": "strong" if args.workload == "cfg3" else "weak", "vs_baseline": None, "dtype": DTYPE[head],
-            "data": "synthetic",
-            "config": {"batch": CFG3_NOTE % (args.frames, world, -(-args.frames // world)) if args.workload == "cfg3" else None,
-                       "workload": "cfg2: Trainer.forward(render_full_img=True) for one 512x512 frame per GPU per step: tri-plane encoders "
-                                   "(P3: 2x StyleGAN_zxc: 3x3 / up-sampling convolutions on split-fp16 MFMA HIP kernels with the block glue fused, stride-2 and 1x1 ones on MIOpen, HIP upfirdn2d/fused_bias_act) -> per-frame plane projection -> fused "
-                                   "ray march (P5-P12) over 262144 rays x (64 coarse + 48 fine) = 29.36M radiance-MLP queries -> [1,67,512,512]",
-                       "arithmetic_mode": head, "operand_bits": MODES[head][1],
-                       "headline_rule": "value = the fastest TIMED mode whose operands are not narrower than the reference's fp32 (modes.* holds every timed loop)",
-                       "phase_ms": {"encoders_P3": round(enc_ms, 3), "plane_prepare": round(prep_ms, 3), "ray_march_kernel": round(kms, 3),
-                                    "encoders_P3_inside_the_graph": round(step_ms - kms - prep_ms, 3),
-                                    "note": "encoders_P3_inside_the_graph is a DIFFERENCE (step - march - preparation) and inherits the march's box-to-box and "
-                                            "clock-state spread: the march is timed alone here, straight after an idle period, and runs 1-2 % slower at the "
-                                            "sustained power cap inside the frame loop (profiles/r05_frame_streams.txt holds the per-queue trace of a replay: "
-                                            "the encoder phase ends 1.72-1.82 ms after the previous march).  encoders_P3 is timed eagerly on one stream; inside the frame's hipGraph the two encoders run "
-                                            "on two streams without launch gaps: step - march - preparation"},
-                       "stage_two": ({"upsampler_ms": round(cfg4_ms, 3), "output": [1, 3, 2 * H, 2 * W],
-                                      "what": "BASELINE configs[3]: the step is the cfg2 frame below followed by SWGAN_unet(512 -> 1024) on render[:, 3:] "
-                                              "(avatarHD_reenactment.py:153-160): its 3x3 / up-sampling convolutions, Haar transforms, upfirdn2d and "
-                                              "fused_bias_act are kernels of this library, stride-2 / 1x1 convolutions MIOpen; phase_ms.encoders_P3_inside_the_graph "
-                                              "includes the upsampler in this workload"} if args.workload == "cfg4" else None),
-                       "rays_per_frame": H * W, "num_coarse": S_C, "num_fine": S_F, "perturb": perturb, "hipgraph": bool(args.graph), "frames_per_replay": frames_per_replay,
-                       "hipgraph_packet_capture": hipgraph_state(),          # in_force = the variable was 0 before this process's first HIP call (ROCm graph-replay fault, havatar_amd/__init__.py)
-                       "parallelism": ("frames sharded, %d rank(s), one overlapped all_gather of finished frames per round" if args.workload == "cfg3"
-                                       else "frames sharded, %d rank(s), no data-path collective") % world,
-                       "exchange": (("RCCL all_gather_into_tensor from a side stream, %d-rank group%s" % (world, " (forced at N = 1)" if world == 1 else ""))
-                                    if (args.workload == "cfg3" and gather is not None and gather.collective) else None),
-                       "kernel": kname},
+        res["config"].update(kernel=kname,
+                             phase_ms={"encoders_P3": round(enc_ms, 3), "plane_prepare": round(prep_ms, 3), "ray_march_kernel": round(kms, 3),
+                                       "encoders_P3_inside_the_graph": round(step_ms - kms - prep_ms, 3),
+                                       "note": "encoders_P3_inside_the_graph is a DIFFERENCE (step - march - preparation) and inherits the march's box-to-box and "
+                                               "clock-state spread: the march is timed alone here, straight after an idle period, and runs 1-2 % slower at the "
+                                               "sustained power cap inside the frame loop (profiles/r05_frame_streams.txt holds the per-queue trace of a replay: "
+                                               "the encoder phase ends 1.72-1.82 ms after the previous march).  encoders_P3 is timed eagerly on one stream; inside the frame's hipGraph the two encoders run "
+                                               "on two streams without launch gaps: step - march - preparation"})
+        if args.workload == "cfg4":
+            res["config"]["stage_two"]["upsampler_ms"] = round(cfg4_ms, 3)
+        res.update({
             "roofline": {"bound": "mfma",
                          "limited_by": ("package power (PPT): under this kernel's load the firmware holds the shader clock below its 2.4 GHz maximum "
                                         "(roofline.power; profiles/r04_throttle_status.txt: PPT violation active, thermal limiters idle; DESIGN.md "
@@ -799,7 +875,7 @@ def main():
                          "mfma_instructions_per_launch_model": rf["mfma_instructions_per_launch_model"],
                          "hbm_algorithmic_bytes_per_launch": BYTES_PER_FRAME,
                          "hbm_achieved_GBps": round(BYTES_PER_FRAME / (kms * 1e-3) / 1e9, 2), "hbm_frac_of_8TBps": round(BYTES_PER_FRAME / (kms * 1e-3) / 8e12, 5)},
-        }
+        })
         # every arithmetic mode that was timed: its own loop (same W / K), its own kernel time
         res["modes"] = {}
         for mode in mode_list:

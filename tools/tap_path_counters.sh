@@ -6,7 +6,7 @@ set -u
 cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/tapc; rm -rf $OUT; mkdir -p $OUT
-BENCH="python bench.py --steps 4 --warmup 1 --no-cpu-baseline"
+BENCH="python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline"
 run() {   # $1 = tag, env HAVATAR_LIB optional
   i=0
   for pass in "TA_TA_BUSY_sum TA_FLAT_READ_WAVEFRONTS_sum GRBM_GUI_ACTIVE" "TCP_TCC_READ_REQ_sum TCP_PENDING_STALL_CYCLES_sum TCP_TCP_TA_DATA_STALL_CYCLES_sum" \
