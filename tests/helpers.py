@@ -163,3 +163,125 @@ def report(line):
             f.write(line + "\n")
     except OSError:
         pass
+
+
+# ---- the training path's reference statements, shared by tests/test_ops_gpu.py, tests/test_mlp_train_gpu.py and tests/test_train_edges_gpu.py
+def _field_inputs_reference(pts, inv_T, vol, planes, nerf_box, skin_box):
+    """PyTorch statement: Deformation_Field_new.forward -> box warp -> sample_from_triplane_new + Embedder -> cat (any dtype)."""
+    import torch
+    from havatar_amd.utils.util import sample_from_triplane_new, voxel_feature
+    B = pts.shape[0]
+    ident = torch.cat([torch.eye(3), torch.zeros(1, 3)], 0).to(pts).unsqueeze(0).expand(B, -1, -1)
+    t = lambda v: torch.tensor(v).to(pts)
+    p_i = [torch.matmul(pts + T[:, -1:], T[:, :3, :3]) for T in (ident, inv_T)]
+    w_c = vol.expand(B, -1, -1, -1, -1)
+    w = torch.cat([voxel_feature(xyz=p * t(skin_box[0]) + t(skin_box[1]), volume_feat=w_c[:, i:i + 1]) for i, p in enumerate(p_i)], -1)
+    w = w / (w.sum(dim=-1, keepdim=True) + 1e-8)
+    rot = w[:, :, 0:1] * p_i[0] + w[:, :, 1:2] * p_i[1]
+    f = sample_from_triplane_new(rot * t(nerf_box[0]) + t(nerf_box[1]), planes, padding_mode="zeros")
+    f = f.reshape(-1, f.shape[-1] * f.shape[-2])
+    x = rot.reshape(-1, 3)
+    from havatar_amd.model.network.embedder import get_embedder
+    return torch.cat([f, get_embedder(multires=8, input_dims=3, include_input=False)[0](x)], -1)
+
+
+NAMES = ("W1", "b1", "W2", "b2", "Wa", "ba", "Wf", "bf", "Wc", "bc")
+
+
+def _weights(dev, scale=1.0, dtype=None):
+    import torch
+    dtype = torch.float32 if dtype is None else dtype
+    m = synth.scene(4, 4, "primary")["mlp"]
+    return [torch.from_numpy(np.ascontiguousarray(m[k] * (scale if k.startswith("W") else 1.0))).to(dev, dtype).requires_grad_(True) for k in NAMES]
+
+
+def _ref_forward(X, ws, bf16=False):
+    """The reference statement; bf16=True rounds exactly the operands the kernel rounds (weights and the inputs of every matrix
+    product), with everything else -- accumulation, biases, the alpha and rgb rows -- in the given dtype."""
+    import torch
+    W1, b1, W2, b2, Wa, ba, Wf, bf, Wc, bc = ws
+    r = (lambda t: t.to(torch.bfloat16).to(t.dtype)) if bf16 else (lambda t: t)
+    h1 = torch.relu(r(X) @ r(W1).t() + b1)
+    h2 = torch.relu(r(h1) @ r(W2).t() + b2)
+    a = h2 @ Wa.t() + ba
+    g = r(h2) @ r(Wf).t() + bf
+    c = g @ Wc.t() + bc
+    return torch.cat([c, g, a], -1)
+
+
+def _inputs(n, dev, seed=0):
+    import torch
+    g = torch.Generator().manual_seed(seed)
+    X = torch.cat([0.5 * torch.randn(n, 128, generator=g), torch.sin(8.0 * torch.randn(n, 48, generator=g))], 1)   # features | encoding
+    d = torch.randn(n, 68, generator=g) / n
+    return X.to(dev), d.to(dev)
+
+
+def check_mlp_forward(n):
+    """hav_mlp_train_fwd at n rows against the reference statement (tests/test_mlp_train_gpu.py, tests/test_train_edges_gpu.py)"""
+    import torch
+    from havatar_amd.native import mlp_train
+    dev = torch.device("cuda:0")
+    ws = _weights(dev)
+    X, _ = _inputs(n, dev)
+    rf = mlp_train.forward_only(X, mlp_train.pack(ws))
+    ref64 = _ref_forward(X.double(), [w.double() for w in ws])
+    emu = _ref_forward(X.double(), [w.double() for w in ws], bf16=True)
+    scale = ref64.abs().max().item()
+    assert rf.shape == (n, 68) and torch.isfinite(rf).all()
+    assert (rf.double() - emu).abs().max().item() <= 1e-3 * scale        # same roundings; fp32-vs-fp64 accumulation flips a bf16 rounding here and there
+    assert (rf.double() - ref64).abs().max().item() <= 2e-2 * scale      # bf16 operands: 2^-9 relative per operand
+    assert (emu - ref64).abs().max().item() >= 0.2 * (rf.double() - ref64).abs().max().item()     # i.e. the error IS the bf16 rounding
+
+
+def check_mlp_backward(n):
+    """dX and all ten parameter gradients against fp64 autograd, with the error a bf16-operand emulation of the same statement makes
+    as the yardstick: the kernel's gradients are bf16-class, not worse."""
+    import torch
+    from havatar_amd.native import mlp_train
+    dev = torch.device("cuda:0")
+    ws = _weights(dev)
+    X, d = _inputs(n, dev)
+    Xg = X.clone().requires_grad_(True)
+    out = mlp_train.fused_mlp(Xg, ws)
+    out.backward(d)
+    got = [Xg.grad] + [w.grad for w in ws]
+    # fp64 truth and the bf16-operand emulation (autograd through the rounding as identity = what the kernel implements)
+    def grads(bf16):
+        w64 = [w.detach().double().requires_grad_(True) for w in ws]
+        x64 = X.double().requires_grad_(True)
+        if bf16:
+            class R(torch.autograd.Function):
+                @staticmethod
+                def forward(ctx, t):
+                    return t.to(torch.bfloat16).to(t.dtype)
+
+                @staticmethod
+                def backward(ctx, gout):
+                    return gout
+            W1, b1, W2, b2, Wa, ba, Wf, bf, Wc, bc = w64
+            h1 = torch.relu(R.apply(x64) @ R.apply(W1).t() + b1)
+            h2 = torch.relu(R.apply(h1) @ R.apply(W2).t() + b2)
+            o = torch.cat([(R.apply(h2) @ R.apply(Wf).t() + bf) @ Wc.t() + bc, R.apply(h2) @ R.apply(Wf).t() + bf, h2 @ Wa.t() + ba], -1)
+        else:
+            o = _ref_forward(x64, w64)
+        o.backward(d.double())
+        return [x64.grad] + [w.grad for w in w64]
+    ref, emu = grads(False), grads(True)
+    for name, g, r, e in zip(("X",) + NAMES, got, ref, emu):
+        scale = r.abs().max().item()
+        err = (g.double() - r).abs().max().item()
+        floor = (e - r).abs().max().item()
+        assert g.shape == r.shape and torch.isfinite(g).all(), name
+        # L-inf: not worse than the emulation.  bf16 operands move a pre-activation by ~1e-3 of the layer's scale, so a relu unit that
+        # sits that close to zero switches on or off and its whole gradient term appears or vanishes: an O(1) error in the few
+        # entries it touches, for the kernel and for the emulation alike (not necessarily the same units: hence the factor).
+        out_layer = name in ("Wa", "ba", "Wf", "bf", "Wc", "bc")
+        if not out_layer:
+            assert err <= 3.0 * floor + 2e-3 * scale, (name, err / scale, floor / scale)
+        # L2: the switches are rare (~1 % of the units), so in norm the gradients are 2e-2-class
+        if n >= 1000:
+            rel2 = ((g.double() - r).norm() / r.norm()).item()
+            assert rel2 <= 8e-2, (name, rel2)
+        if out_layer:          # no relu switch between them and the loss: plain bf16 rounding of their operands (the kernel also rounds
+            assert err <= 2e-2 * scale, (name, err / scale)       # the upstream gradient, which the emulation does not)

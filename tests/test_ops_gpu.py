@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import GOLDEN, linf
+from helpers import GOLDEN, _field_inputs_reference, linf
 from havatar_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -556,24 +556,6 @@ def test_triplane_gather_forward_and_gradients_match_grid_sample():
             e_mine = (mine.double() - r64).abs().max().item() / scale
             e_aten = (r32.double() - r64).abs().max().item() / scale
             assert e_mine <= max(2.0 * e_aten, 2e-6), (name, e_mine, e_aten)
-
-
-def _field_inputs_reference(pts, inv_T, vol, planes, nerf_box, skin_box):
-    """PyTorch statement: Deformation_Field_new.forward -> box warp -> sample_from_triplane_new + Embedder -> cat (any dtype)."""
-    from havatar_amd.utils.util import sample_from_triplane_new, voxel_feature
-    B = pts.shape[0]
-    ident = torch.cat([torch.eye(3), torch.zeros(1, 3)], 0).to(pts).unsqueeze(0).expand(B, -1, -1)
-    t = lambda v: torch.tensor(v).to(pts)
-    p_i = [torch.matmul(pts + T[:, -1:], T[:, :3, :3]) for T in (ident, inv_T)]
-    w_c = vol.expand(B, -1, -1, -1, -1)
-    w = torch.cat([voxel_feature(xyz=p * t(skin_box[0]) + t(skin_box[1]), volume_feat=w_c[:, i:i + 1]) for i, p in enumerate(p_i)], -1)
-    w = w / (w.sum(dim=-1, keepdim=True) + 1e-8)
-    rot = w[:, :, 0:1] * p_i[0] + w[:, :, 1:2] * p_i[1]
-    f = sample_from_triplane_new(rot * t(nerf_box[0]) + t(nerf_box[1]), planes, padding_mode="zeros")
-    f = f.reshape(-1, f.shape[-1] * f.shape[-2])
-    x = rot.reshape(-1, 3)
-    from havatar_amd.model.network.embedder import get_embedder
-    return torch.cat([f, get_embedder(multires=8, input_dims=3, include_input=False)[0](x)], -1)
 
 
 def test_field_inputs_forward_and_gradients_match_the_pytorch_statement():
