@@ -10,7 +10,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libhavatar_hip.so")
 
 HAV_F32, HAV_F16, HAV_BF16, HAV_F64 = 0, 1, 2, 3
 HAV_MLP_SPLIT_BF16, HAV_MLP_F32, HAV_MLP_SPLIT_F16, HAV_MLP_SPLIT_F16_MX = 0, 1, 2, 3
-ABI_VERSION = 6
+ABI_VERSION = 7
 HAV_FLAG_PAIR_KERNEL, HAV_FLAG_FINE_CACHE, HAV_FLAG_FINE_RECOMPUTE, HAV_FLAG_NO_FP16_GUARD = 1, 2, 4, 8
 HAV_STATUS_FP16_FALLBACK = 1
 
@@ -203,6 +203,19 @@ def lib():
     L.hav_gen_rays.restype = i32
     L.hav_debug_mlp_layer.argtypes = [vp, vp, vp, i32, i32, i64, vp]
     L.hav_debug_mlp_layer.restype = i32
+    L.hav_conv3d_k3_packed_bytes.argtypes = [i32, i32]
+    L.hav_conv3d_k3_packed_bytes.restype = i64
+    for fn in (L.hav_conv3d_k3_pack, L.hav_conv3d_k3_pack_t):
+        fn.argtypes = [vp, vp, i32, i32, f32, vp]
+        fn.restype = i32
+    L.hav_conv3d_k3_scratch_bytes.argtypes = [i32] * 6
+    L.hav_conv3d_k3_scratch_bytes.restype = i64
+    L.hav_conv3d_k3_fwd.argtypes = [vp] * 5 + [i32] * 6 + [vp, vp]
+    L.hav_conv3d_k3_fwd.restype = i32
+    L.hav_conv3d_k3_wgrad_scratch_bytes.argtypes = [i32] * 6
+    L.hav_conv3d_k3_wgrad_scratch_bytes.restype = i64
+    L.hav_conv3d_k3_wgrad.argtypes = [vp] * 7 + [i32] * 6 + [vp]
+    L.hav_conv3d_k3_wgrad.restype = i32
     _lib = L
     return L
 

@@ -1,7 +1,11 @@
 """VolumeDecoder: learned constant -> 6x(trilinear x2, Conv3d 3^3, InstanceNorm3d, ReLU) -> Conv3d -> sigmoid -> [1,2,R,R,R]
-(reference model/network/voxel_encoder.py:150-210).  Producer of the skinning volume; stays PyTorch (MIOpen Conv3d).
+(reference model/network/voxel_encoder.py:150-210).  Producer of the skinning volume.  Its 3x3x3 layers on <= 8^3 voxels run as GEMMs over
+a patch matrix (native/train_ops.py::Conv3dSmall); the 16^3 - 64^3 layers stay on nn.Conv3d (MIOpen) by default and take this library's
+own split-fp16 kernels (native/train_ops.py::Conv3dK3, csrc/hav_conv3d.hip) with HAVATAR_CONV3D=hip.  final_conv (16 -> 1 output
+channel) stays on nn.Conv3d either way.
 state_dict keys: init_lc, filters.{i}.up.1.{weight,bias}, final_conv.{weight,bias}."""
 import math
+import os
 
 import torch
 import torch.nn as nn
@@ -47,11 +51,15 @@ class UpConv3DBlock(nn.Module):
 
     def forward(self, x):
         if isinstance(self.up, nn.Sequential) and x.is_cuda:
-            from ...native.train_ops import conv3d_small, conv3d_small_eligible
+            from ...native.train_ops import conv3d_k3_eligible, conv3d_small, conv3d_small_eligible
             y = self.up[0](x)
             if conv3d_small_eligible(y, self.up[1]):
                 # volumes of <= 8^3 voxels: the convolution as GEMMs over an explicit patch matrix (native/train_ops.py::Conv3dSmall)
                 return self.norm(conv3d_small(y, self.up[1]))
+            if conv3d_k3_eligible(y, self.up[1]) and os.environ.get("HAVATAR_CONV3D") == "hip":
+                # opt-in: the 16^3 - 64^3 layers on the native 3x3x3 kernels (native/train_ops.py::Conv3dK3); MIOpen stays the default
+                from ...native import train_ops
+                return self.norm(train_ops.conv3d_k3(y, self.up[1]))
             return self.norm(self.up[1](y))
         return self.norm(self.up(x))
 

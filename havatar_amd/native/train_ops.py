@@ -368,6 +368,114 @@ def conv3d_small(x, conv):
     return Conv3dSmall.apply(x, conv.weight, conv.bias)
 
 
+_K3_BLOBS = {}          # (weight data pointer, transposed, stream) -> (weak reference, key, blob)
+
+
+def _conv3d_k3_blob(w, transposed):
+    """The fragment blob of w [Cout,Cin,3,3,3] (hav_conv3d_k3_pack) or of its data gradient's filters (hav_conv3d_k3_pack_t), packed on the
+    current stream.  Cached per weight tensor and stream, keyed by data pointer, `_version` and graph.weights_epoch(); never while a stream
+    is capturing (the pack has to be part of a captured step: its weights change between replays).  The stream is part of the slot because a
+    blob is only ordered behind its pack on the stream that packed it; entries whose weight tensor is gone are dropped at the next pack."""
+    import weakref
+    from ..graph import weights_epoch
+    capturing = torch.cuda.is_current_stream_capturing()
+    slot, key = (w.data_ptr(), transposed, torch.cuda.current_stream(w.device).cuda_stream), (w._version, weights_epoch(), w.device)
+    hit = _K3_BLOBS.get(slot)
+    if not capturing and hit is not None and hit[0]() is w and hit[1] == key:
+        return hit[2]
+    Cout, Cin = w.shape[:2]
+    L = _lib.lib()
+    n = int(L.hav_conv3d_k3_packed_bytes(Cin, Cout) if transposed else L.hav_conv3d_k3_packed_bytes(Cout, Cin))
+    blob = torch.empty(n, dtype=torch.uint8, device=w.device)
+    with torch.cuda.device(w.device):
+        fn, name = (L.hav_conv3d_k3_pack_t, "hav_conv3d_k3_pack_t") if transposed else (L.hav_conv3d_k3_pack, "hav_conv3d_k3_pack")
+        _lib.check(fn(_p(blob), _p(w), Cout, Cin, 1.0, _stream()), name)
+    if not capturing:
+        for k in [k for k, v in _K3_BLOBS.items() if v[0]() is None]:
+            del _K3_BLOBS[k]
+        _K3_BLOBS[slot] = (weakref.ref(w), key, blob)
+    return blob
+
+
+def _conv3d_k3_run(y, x, blob, bias, amax, B, Cin, Cout, D, H, W):
+    L = _lib.lib()
+    n = int(L.hav_conv3d_k3_scratch_bytes(B, Cin, Cout, D, H, W))
+    scratch = torch.empty(n, dtype=torch.uint8, device=x.device) if n else None
+    _lib.check(L.hav_conv3d_k3_fwd(_p(y), _p(x), _p(blob), _p(bias), _p(amax), B, Cin, Cout, D, H, W, _p(scratch), _stream()), "hav_conv3d_k3_fwd")
+
+
+class Conv3dK3(Function):
+    """nn.Conv3d(kernel 3, padding 1, stride 1, zeros) on the split-fp16 matrix path (hav_conv3d_k3_*: csrc/hav_conv3d.hip), NCDHW float32
+    with no layout transposes: the 16^3 - 64^3 layers of VolumeDecoder.  Both the activations and the gradient go through hav_absmax
+    (power-of-two range control); every buffer comes from torch.empty and nothing synchronises, so the node can be captured."""
+
+    @staticmethod
+    @_fwd32
+    def forward(ctx, x, w, b):
+        from .conv import absmax
+        _need_hip("Conv3dK3", x, w, b)
+        x = x.contiguous()
+        wp = w if w.is_contiguous() else w.contiguous()
+        B, Cin, D, H, W = x.shape
+        Cout = w.shape[0]
+        y = torch.empty(B, Cout, D, H, W, device=x.device, dtype=torch.float32)
+        x_amax = absmax(x)
+        blob = _conv3d_k3_blob(wp.detach() if wp is not w else w, False)
+        with torch.cuda.device(x.device):
+            _conv3d_k3_run(y, x, blob, b.contiguous() if b is not None else None, x_amax, B, Cin, Cout, D, H, W)
+        ctx.save_for_backward(x, w, x_amax)
+        ctx.has_bias = b is not None
+        return y
+
+    @staticmethod
+    @once_differentiable
+    @_bwd32
+    def backward(ctx, g):
+        from .conv import absmax
+        x, w, x_amax = ctx.saved_tensors
+        B, Cin, D, H, W = x.shape
+        Cout = w.shape[0]
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
+        dx = dw = db = None
+        if not (need_x or need_w or need_b):
+            return None, None, None
+        g = g.contiguous()
+        g_amax = absmax(g)
+        L = _lib.lib()
+        with torch.cuda.device(g.device):
+            if need_x:
+                dx = torch.empty_like(x)
+                _conv3d_k3_run(dx, g, _conv3d_k3_blob(w if w.is_contiguous() else w.contiguous(), True), None, g_amax, B, Cout, Cin, D, H, W)
+            if need_w or need_b:
+                dw = torch.empty(Cout, Cin, 3, 3, 3, device=g.device, dtype=torch.float32) if need_w else None          # None: bias sums alone
+                db = torch.empty(Cout, device=g.device, dtype=torch.float32) if need_b else None
+                scratch = torch.empty(int(L.hav_conv3d_k3_wgrad_scratch_bytes(B, Cin, Cout, D, H, W)), dtype=torch.uint8, device=g.device)
+                _lib.check(L.hav_conv3d_k3_wgrad(_p(dw), _p(db), _p(g), _p(x), _p(scratch), _p(g_amax), _p(x_amax), B, Cin, Cout, D, H, W,
+                                                 _stream()), "hav_conv3d_k3_wgrad")
+        return dx, dw, db
+
+
+def conv3d_k3_eligible(x, conv):
+    """The parameter checks of conv3d_small_eligible plus the shape constraints of hav_conv3d_k3_* (include/havatar.h): Cin, Cout in
+    {16, 32, 64, 128}, W % 16 == 0, 32-bit offsets inside one sample."""
+    w, b = conv.weight, conv.bias
+    if not (w.is_cuda and w.device == x.device and w.dtype == torch.float32 and (b is None or (b.dtype == torch.float32 and b.device == x.device))
+            and getattr(conv, "padding_mode", "zeros") == "zeros"):
+        return False
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 5 and w.dim() == 5
+            and tuple(conv.kernel_size) == (3, 3, 3) and tuple(conv.padding) == (1, 1, 1) and tuple(conv.stride) == (1, 1, 1)
+            and tuple(conv.dilation) == (1, 1, 1) and conv.groups == 1):
+        return False
+    B, Cin, D, H, W = x.shape
+    Cout = w.shape[0]
+    return (w.shape[1] == Cin and Cin in (16, 32, 64, 128) and Cout in (16, 32, 64, 128) and W >= 16 and W % 16 == 0 and D >= 1 and H >= 1
+            and 1 <= B <= 65535 and max(Cin, Cout) * D * H * W < 2 ** 31)
+
+
+def conv3d_k3(x, conv):
+    return Conv3dK3.apply(x, conv.weight, conv.bias)
+
+
 class Demod(Function):
     """d [B,Cout] = rsqrt(sum_i s[b,i]^2 * scale^2 sum_k W[o,i,k]^2 + eps): the demodulation factors of a ModulatedConv2d
     (reference model/styleUnet.py:214-227, factored form) as one autograd node -- two launches each way (hav_demod_fwd / _bwd)

@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define HAV_ABI_VERSION 6
+#define HAV_ABI_VERSION 7
 
 #define HAV_EINVAL   (-1) /* bad size / null pointer / inconsistent arguments            */
 #define HAV_EUNSUP   (-2) /* valid for the reference, not supported by this build        */
@@ -308,6 +308,40 @@ int hav_gemm_split(float* y /*[B,M,N]*/, const float* x /*[B,K,N]*/, const void*
 int hav_upconv_finish(float* y, const float* col, const float* fir4x4, const float* d, const float* noise, const float* noise_weight,
                       const float* bias, float slope, float gain, int act, int noise_batched, int B, int Cout, int H, int W,
                       void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * 3x3x3, stride-1, zero-padding-1 convolution of the skinning-volume decoder, forward, data gradient and weight gradient (ABI 7) --
+ * replaces nn.Conv3d of UpConv3DBlock / VolumeDecoder (model/network/voxel_encoder.py:183-210; the reference runs it through ATen:
+ * MIOpen / CK fp32 kernels + NCDHW <-> NDHWC transposes around each call):
+ *   y[b,o,z,y,x] = bias[o] + sum_{i,kz,ky,kx} w[o,i,kz,ky,kx] * x[b,i,z+kz-1,y+ky-1,x+kx-1]
+ * x [B,Cin,D,H,W], y [B,Cout,D,H,W]: float32, NCDHW, contiguous, no transposes.  Arithmetic as hav_conv3x3_split: implicit GEMM
+ * (K = 27 Cin) on v_mfma_f32_32x32x16_f16, operands split into hi + lo fp16, three products, fp32 accumulation: fp32-class results.
+ * Bit-reproducible: no float atomics; K-split slices are added in slice order by a second pass.
+ * Supported: Cin, Cout in {16, 32, 64, 128}; W % 16 == 0; D, H >= 1 free; max(Cin, Cout) * D * H * W < 2^31; B <= 65535.  Anything else
+ * returns HAV_EUNSUP before a launch and leaves every output untouched (the caller keeps its MIOpen route).
+ *   hav_conv3d_k3_packed_bytes  0 for channel counts the packs refuse
+ *   hav_conv3d_k3_pack     the MFMA-fragment-ordered split weight blob of w [Cout,Cin,3,3,3] * wmul (hav_conv3d_k3_packed_bytes bytes)
+ *   hav_conv3d_k3_pack_t   the blob of the DATA GRADIENT of the convolution with filters w [Cout_w,Cin_w,3,3,3]: the convolution with
+ *                          Cin_w output and Cout_w input channels and filters W'[i][o][t] = w[o][i][26 - t], packed straight from w
+ *                          (hav_conv3d_k3_packed_bytes(Cin_w, Cout_w) bytes)
+ *   hav_conv3d_k3_fwd      the convolution; through a _pack_t blob (Cin, Cout swapped, bias NULL) it is the data gradient.  bias [Cout]
+ *                          nullable.  in_amax: HAV_ABSMAX_WORDS words of hav_absmax(x) or NULL -- range control as in hav_conv3x3_split
+ *                          (mandatory for gradient-sized or 1e5-sized inputs).  scratch: hav_conv3d_k3_scratch_bytes() bytes (small
+ *                          volumes split the channel range over 2-8 workgroups; 0: not needed; NULL: never split)
+ *   hav_conv3d_k3_wgrad    gw[o,i,kz,ky,kx] = sum_{b,z,y,x} g[b,o,z,y,x] * x[b,i,z+kz-1,y+ky-1,x+kx-1];  gbias[o] = sum g[b,o,...]
+ *                          (either output nullable, not both: gw NULL runs the bias sums alone).  scratch: hav_conv3d_k3_wgrad_scratch_bytes() bytes (K-split partial sums, always needed);
+ *                          g_amax / x_amax: hav_absmax words of g / x or NULL (power-of-two range control of either operand)
+ * ------------------------------------------------------------------------------------------ */
+int64_t hav_conv3d_k3_packed_bytes(int Cout, int Cin);
+int hav_conv3d_k3_pack(void* packed, const float* w, int Cout, int Cin, float wmul, void* stream);
+int hav_conv3d_k3_pack_t(void* packed, const float* w, int Cout_w, int Cin_w, float wmul, void* stream);
+int64_t hav_conv3d_k3_scratch_bytes(int B, int Cin, int Cout, int D, int H, int W);
+int hav_conv3d_k3_fwd(float* y, const float* x, const void* packed, const float* bias, const void* in_amax, int B, int Cin, int Cout,
+                      int D, int H, int W, void* scratch, void* stream);
+int64_t hav_conv3d_k3_wgrad_scratch_bytes(int B, int Cin, int Cout, int D, int H, int W);
+int hav_conv3d_k3_wgrad(float* gw /*[Cout,Cin,3,3,3] or NULL*/, float* gbias /*[Cout] or NULL*/, const float* g /*[B,Cout,D,H,W]*/,
+                        const float* x /*[B,Cin,D,H,W]*/, void* scratch, const void* g_amax, const void* x_amax, int B, int Cin, int Cout,
+                        int D, int H, int W, void* stream);
 
 /* Haar analysis / synthesis of SWGAN_unet's wavelet-domain skip path (model/styleUnet.py HaarTransform / InverseHaarTransform: four
  * upfirdn2d calls each, + cat / + three adds) as one pass each, bit-identical to the four-call sequence.
