@@ -10,7 +10,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libhavatar_hip.so")
 
 HAV_F32, HAV_F16, HAV_BF16, HAV_F64 = 0, 1, 2, 3
 HAV_MLP_SPLIT_BF16, HAV_MLP_F32, HAV_MLP_SPLIT_F16, HAV_MLP_SPLIT_F16_MX = 0, 1, 2, 3
-ABI_VERSION = 7
+ABI_VERSION = 8
 HAV_FLAG_PAIR_KERNEL, HAV_FLAG_FINE_CACHE, HAV_FLAG_FINE_RECOMPUTE, HAV_FLAG_NO_FP16_GUARD = 1, 2, 4, 8
 HAV_STATUS_FP16_FALLBACK = 1
 
@@ -216,6 +216,19 @@ def lib():
     L.hav_conv3d_k3_wgrad_scratch_bytes.restype = i64
     L.hav_conv3d_k3_wgrad.argtypes = [vp] * 7 + [i32] * 6 + [vp]
     L.hav_conv3d_k3_wgrad.restype = i32
+    for fn in (L.hav_inorm_relu_chunks, L.hav_inorm_relu_scratch_bytes):
+        fn.argtypes = [i64, i64]
+        fn.restype = i64
+    L.hav_inorm_relu_fwd.argtypes = [vp] * 4 + [i64, i64, f32, vp, vp]
+    L.hav_inorm_relu_fwd.restype = i32
+    L.hav_inorm_relu_bwd.argtypes = [vp] * 5 + [i64, i64, vp, vp]
+    L.hav_inorm_relu_bwd.restype = i32
+    L.hav_final_conv_sigmoid_fwd.argtypes = [vp] * 4 + [i32] * 6 + [vp]
+    L.hav_final_conv_sigmoid_fwd.restype = i32
+    L.hav_final_conv_sigmoid_bwd_scratch_bytes.argtypes = [i32] * 6
+    L.hav_final_conv_sigmoid_bwd_scratch_bytes.restype = i64
+    L.hav_final_conv_sigmoid_bwd.argtypes = [vp] * 8 + [i32] * 6 + [vp]
+    L.hav_final_conv_sigmoid_bwd.restype = i32
     _lib = L
     return L
 

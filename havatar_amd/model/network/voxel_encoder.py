@@ -1,8 +1,9 @@
 """VolumeDecoder: learned constant -> 6x(trilinear x2, Conv3d 3^3, InstanceNorm3d, ReLU) -> Conv3d -> sigmoid -> [1,2,R,R,R]
 (reference model/network/voxel_encoder.py:150-210).  Producer of the skinning volume.  Its 3x3x3 layers on <= 8^3 voxels run as GEMMs over
 a patch matrix (native/train_ops.py::Conv3dSmall); the 16^3 - 64^3 layers stay on nn.Conv3d (MIOpen) by default and take this library's
-own split-fp16 kernels (native/train_ops.py::Conv3dK3, csrc/hav_conv3d.hip) with HAVATAR_CONV3D=hip.  final_conv (16 -> 1 output
-channel) stays on nn.Conv3d either way.
+own split-fp16 kernels (native/train_ops.py::Conv3dK3, csrc/hav_conv3d.hip) with HAVATAR_CONV3D=hip.  HAVATAR_DECODER=hip implies that
+route and also takes InstanceNorm3d + ReLU (train_ops.inorm_relu3d) and final_conv + sigmoid + cat (train_ops.final_conv_sigmoid) onto
+csrc/hav_decoder.hip; without it both stay the ATen statements.
 state_dict keys: init_lc, filters.{i}.up.1.{weight,bias}, final_conv.{weight,bias}."""
 import math
 import os
@@ -49,19 +50,34 @@ class UpConv3DBlock(nn.Module):
                                     nn.Conv3d(input_nc, output_nc, kernel_size=3, padding=1, stride=1))
         self.norm = nn.InstanceNorm3d(output_nc, affine=False)
 
-    def forward(self, x):
+    def _conv(self, x, native):
         if isinstance(self.up, nn.Sequential) and x.is_cuda:
             from ...native.train_ops import conv3d_k3_eligible, conv3d_small, conv3d_small_eligible
             y = self.up[0](x)
             if conv3d_small_eligible(y, self.up[1]):
                 # volumes of <= 8^3 voxels: the convolution as GEMMs over an explicit patch matrix (native/train_ops.py::Conv3dSmall)
-                return self.norm(conv3d_small(y, self.up[1]))
-            if conv3d_k3_eligible(y, self.up[1]) and os.environ.get("HAVATAR_CONV3D") == "hip":
+                return conv3d_small(y, self.up[1])
+            if conv3d_k3_eligible(y, self.up[1]) and (native or os.environ.get("HAVATAR_CONV3D") == "hip"):
                 # opt-in: the 16^3 - 64^3 layers on the native 3x3x3 kernels (native/train_ops.py::Conv3dK3); MIOpen stays the default
                 from ...native import train_ops
-                return self.norm(train_ops.conv3d_k3(y, self.up[1]))
-            return self.norm(self.up[1](y))
-        return self.norm(self.up(x))
+                return train_ops.conv3d_k3(y, self.up[1])
+            return self.up[1](y)
+        return self.up(x)
+
+    def forward(self, x):
+        return self.norm(self._conv(x, False))
+
+    def forward_relu(self, x):
+        """relu(forward(x)), what VolumeDecoder applies to every block.  With HAVATAR_DECODER=hip the normalisation and the ReLU are one
+        node of this library (native/train_ops.py::InormRelu3d) and the 16^3 - 64^3 convolutions take conv3d_k3; whatever is not
+        eligible keeps today's statements."""
+        if os.environ.get("HAVATAR_DECODER") == "hip" and x.is_cuda:
+            from ...native import train_ops
+            y = self._conv(x, True)
+            if train_ops.inorm_relu3d_eligible(y, self.norm):
+                return train_ops.inorm_relu3d(y, self.norm.eps)
+            return torch.relu(self.norm(y))
+        return torch.relu(self(x))
 
 
 class VolumeDecoder(nn.Module):
@@ -81,6 +97,10 @@ class VolumeDecoder(nn.Module):
     def forward(self):
         x = self.init_lc
         for f in self.filters:
-            x = torch.relu(f(x))
+            x = f.forward_relu(x)
+        if os.environ.get("HAVATAR_DECODER") == "hip" and x.is_cuda:
+            from ...native import train_ops
+            if train_ops.final_conv_sigmoid_eligible(x, self.final_conv):
+                return train_ops.final_conv_sigmoid(x, self.final_conv)
         x = torch.sigmoid(self.final_conv(x))
         return torch.cat([x, 1 - x], dim=1)

@@ -476,6 +476,129 @@ def conv3d_k3(x, conv):
     return Conv3dK3.apply(x, conv.weight, conv.bias)
 
 
+class InormRelu3d(Function):
+    """relu(nn.InstanceNorm3d(affine=False, track_running_stats=False)(y)) as one node (hav_inorm_relu_*: csrc/hav_decoder.hip): ordered fp32
+    statistics (per-chunk mean and M2, merged by the parallel-variance formula), no float atomics, planes of the large layers cut over
+    several workgroups.  Saves y and the per-plane mu, rstd; every buffer (scratch included) comes from torch.empty and nothing
+    synchronises, so the node can be captured."""
+
+    @staticmethod
+    @_fwd32
+    def forward(ctx, y, eps):
+        _need_hip("InormRelu3d", y)
+        y = y.contiguous()
+        NC, V = y.shape[0] * y.shape[1], y.shape[2] * y.shape[3] * y.shape[4]
+        z = torch.empty_like(y)
+        stats = torch.empty(2, NC, device=y.device, dtype=torch.float32)
+        L = _lib.lib()
+        with torch.cuda.device(y.device):
+            n = int(L.hav_inorm_relu_scratch_bytes(NC, V))
+            scratch = torch.empty(n, dtype=torch.uint8, device=y.device) if n else None
+            _lib.check(L.hav_inorm_relu_fwd(_p(z), _p(stats[0]), _p(stats[1]), _p(y), NC, V, float(eps), _p(scratch), _stream()), "hav_inorm_relu_fwd")
+        ctx.save_for_backward(y, stats)
+        return z
+
+    @staticmethod
+    @once_differentiable
+    @_bwd32
+    def backward(ctx, dz):
+        y, stats = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        NC, V = y.shape[0] * y.shape[1], y.shape[2] * y.shape[3] * y.shape[4]
+        dz = dz.contiguous()
+        dy = torch.empty_like(y)
+        L = _lib.lib()
+        with torch.cuda.device(y.device):
+            n = int(L.hav_inorm_relu_scratch_bytes(NC, V))
+            scratch = torch.empty(n, dtype=torch.uint8, device=y.device) if n else None
+            _lib.check(L.hav_inorm_relu_bwd(_p(dy), _p(dz), _p(y), _p(stats[0]), _p(stats[1]), NC, V, _p(scratch), _stream()), "hav_inorm_relu_bwd")
+        return dy, None
+
+
+def inorm_relu3d_eligible(y, norm):
+    """A HIP float32 5-D tensor through an InstanceNorm3d without affine parameters and without running statistics, planes of at least
+    two voxels (with one voxel PyTorch raises in training, and the fallback keeps doing so)."""
+    if not (torch.is_tensor(y) and y.is_cuda and y.dtype == torch.float32 and y.dim() == 5):
+        return False
+    if not isinstance(norm, torch.nn.InstanceNorm3d) or norm.affine or norm.track_running_stats:
+        return False
+    if norm.weight is not None or norm.bias is not None or getattr(norm, "running_mean", None) is not None:
+        return False
+    NC, V = y.shape[0] * y.shape[1], y.shape[2] * y.shape[3] * y.shape[4]
+    return 1 <= NC < 2 ** 31 and 2 <= V < 2 ** 31
+
+
+def inorm_relu3d(y, eps=1e-5):
+    """y [B,C,D,H,W] -> relu(instance_norm(y)), biased variance."""
+    return InormRelu3d.apply(y, eps)
+
+
+FINAL_CONV_MAX_CIN = 64          # FC_MAXC of csrc/hav_decoder.hip: the 27 Cin weights sit in LDS
+
+
+class FinalConvSigmoid(Function):
+    """cat([s, 1 - s], 1), s = sigmoid(nn.Conv3d(Cin, 1, 3, padding 1)(x)), as one node (hav_final_conv_sigmoid_*: csrc/hav_decoder.hip):
+    direct fp32 arithmetic, NCDHW.  Saves x, w and the volume; dx, dw and db come from one call, each only if wanted.  Capturable like
+    Conv3dK3."""
+
+    @staticmethod
+    @_fwd32
+    def forward(ctx, x, w, b):
+        _need_hip("FinalConvSigmoid", x, w, b)
+        x, w = x.contiguous(), w.contiguous()
+        B, Cin, D, H, W = x.shape
+        vol = torch.empty(B, 2, D, H, W, device=x.device, dtype=torch.float32)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.lib().hav_final_conv_sigmoid_fwd(_p(vol), _p(x), _p(w), _p(b.contiguous() if b is not None else None), B, Cin, w.shape[0],
+                                                             D, H, W, _stream()), "hav_final_conv_sigmoid_fwd")
+        ctx.save_for_backward(x, w, vol)
+        ctx.has_bias = b is not None
+        return vol
+
+    @staticmethod
+    @once_differentiable
+    @_bwd32
+    def backward(ctx, dvol):
+        x, w, vol = ctx.saved_tensors
+        B, Cin, D, H, W = x.shape
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
+        if not (need_x or need_w or need_b):
+            return None, None, None
+        dvol = dvol.contiguous()
+        dx = torch.empty_like(x) if need_x else None
+        dw = torch.empty_like(w) if need_w else None
+        db = torch.empty(1, device=x.device, dtype=torch.float32) if need_b else None
+        L = _lib.lib()
+        with torch.cuda.device(x.device):
+            scratch = torch.empty(int(L.hav_final_conv_sigmoid_bwd_scratch_bytes(B, Cin, 1, D, H, W)), dtype=torch.uint8, device=x.device)
+            _lib.check(L.hav_final_conv_sigmoid_bwd(_p(dx), _p(dw), _p(db), _p(dvol), _p(vol), _p(x), _p(w), _p(scratch), B, Cin, 1, D, H, W,
+                                                    _stream()), "hav_final_conv_sigmoid_bwd")
+        return dx, dw, db
+
+
+def final_conv_sigmoid_eligible(x, conv):
+    """The parameter checks of conv3d_k3_eligible with one output channel, Cin <= FINAL_CONV_MAX_CIN and 32-bit offsets inside one sample
+    (any D, H, W >= 1)."""
+    w, b = conv.weight, conv.bias
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 5):
+        return False
+    if not (w.is_cuda and w.device == x.device and w.dtype == torch.float32 and (b is None or (b.dtype == torch.float32 and b.device == x.device))
+            and getattr(conv, "padding_mode", "zeros") == "zeros"):
+        return False
+    if not (w.dim() == 5 and tuple(conv.kernel_size) == (3, 3, 3) and tuple(conv.padding) == (1, 1, 1) and tuple(conv.stride) == (1, 1, 1)
+            and tuple(conv.dilation) == (1, 1, 1) and conv.groups == 1):
+        return False
+    B, Cin, D, H, W = x.shape
+    return (w.shape[0] == 1 and w.shape[1] == Cin and 1 <= Cin <= FINAL_CONV_MAX_CIN and B >= 1 and D >= 1 and H >= 1 and W >= 1
+            and max(Cin, 2, B) * D * H * W < 2 ** 31)
+
+
+def final_conv_sigmoid(x, conv):
+    """x [B,Cin,D,H,W] -> [B,2,D,H,W] = cat([s, 1 - s], 1), s = sigmoid(conv(x))."""
+    return FinalConvSigmoid.apply(x, conv.weight, conv.bias)
+
+
 class Demod(Function):
     """d [B,Cout] = rsqrt(sum_i s[b,i]^2 * scale^2 sum_k W[o,i,k]^2 + eps): the demodulation factors of a ModulatedConv2d
     (reference model/styleUnet.py:214-227, factored form) as one autograd node -- two launches each way (hav_demod_fwd / _bwd)

@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define HAV_ABI_VERSION 7
+#define HAV_ABI_VERSION 8
 
 #define HAV_EINVAL   (-1) /* bad size / null pointer / inconsistent arguments            */
 #define HAV_EUNSUP   (-2) /* valid for the reference, not supported by this build        */
@@ -342,6 +342,51 @@ int64_t hav_conv3d_k3_wgrad_scratch_bytes(int B, int Cin, int Cout, int D, int H
 int hav_conv3d_k3_wgrad(float* gw /*[Cout,Cin,3,3,3] or NULL*/, float* gbias /*[Cout] or NULL*/, const float* g /*[B,Cout,D,H,W]*/,
                         const float* x /*[B,Cin,D,H,W]*/, void* scratch, const void* g_amax, const void* x_amax, int B, int Cin, int Cout,
                         int D, int H, int W, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * ABI 8: InstanceNorm3d + ReLU of the skinning-volume decoder (csrc/hav_decoder.hip).  Replaces, per UpConv3DBlock, `self.norm(...)`
+ * (reference model/network/voxel_encoder.py:183-210, the norm at :198 / :205: nn.InstanceNorm3d(output_nc, affine=False), no running
+ * statistics) and the `self.relu` that VolumeDecoder.forward applies to the block's output (model/network/voxel_encoder.py:171-172), forward and backward.
+ *   z = relu((y - mu) * rstd),  mu = mean(y),  rstd = 1 / sqrt(biased var(y) + eps)      per plane of V contiguous floats, NC planes
+ *   dy = rstd * (gm - mean(gm) - xh * mean(gm * xh)),  xh = (y - mu) * rstd,  gm = dz * [xh > 0]
+ * float32; 16-byte accesses when V % 4 == 0 and the buffers are 16-byte aligned, 4-byte ones otherwise.  Statistics are mean and M2 of
+ * sub-chunks merged in ascending order by the parallel-variance formula; no float atomics: bit-reproducible.
+ *   hav_inorm_relu_chunks          pieces a plane is cut into for (NC, V) on this device: 1 = a single owner (one wave for V <= 256, else
+ *                                  one workgroup) does everything in one launch; > 1 = pieces of a multiple of 1024 voxels over several
+ *                                  workgroups (V > 4096 and NC < 2 CUs), partial results in `scratch`, a merging launch, an apply launch.
+ *                                  Grids are capped at 4 workgroups per CU (one-wave owners: 4 planes per workgroup) and walked with a
+ *                                  grid stride.  0 for sizes the calls refuse.
+ *   hav_inorm_relu_scratch_bytes   bytes of `scratch` both calls need (0: none, the pointer may be NULL)
+ *   hav_inorm_relu_fwd             writes z [NC,V], mu [NC], rstd [NC]
+ *   hav_inorm_relu_bwd             writes dy [NC,V] from dz, y and the forward's mu, rstd
+ * NULL pointers, NC < 1, V < 2, eps < 0: HAV_EINVAL; NC or V >= 2^31: HAV_EUNSUP; both before any launch, outputs untouched.
+ * ------------------------------------------------------------------------------------------ */
+int64_t hav_inorm_relu_chunks(int64_t NC, int64_t V);
+int64_t hav_inorm_relu_scratch_bytes(int64_t NC, int64_t V);
+int hav_inorm_relu_fwd(float* z, float* mu, float* rstd, const float* y, int64_t NC, int64_t V, float eps, void* scratch, void* stream);
+int hav_inorm_relu_bwd(float* dy, const float* dz, const float* y, const float* mu, const float* rstd, int64_t NC, int64_t V, void* scratch,
+                       void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * ABI 8: the decoder's output layer (csrc/hav_decoder.hip).  Replaces `x = torch.sigmoid(self.final_conv(x)); torch.cat([x, 1 - x], 1)`
+ * (reference model/network/voxel_encoder.py:175-178, final_conv = nn.Conv3d(Cin, 1, 3, padding 1) of :164: the tail of the decoder whose
+ * blocks are model/network/voxel_encoder.py:183-210), forward and backward.
+ *   vol[b,0] = s = sigmoid(bias + sum_{c,t} w[0,c,t] x[b,c,p + off(t)]),  vol[b,1] = 1 - s           x [B,Cin,D,H,W], vol [B,2,D,H,W]
+ *   gs = (dvol[b,0] - dvol[b,1]) s (1 - s);  dx[b,c,p] = sum_t w[0,c,t] gs[b,p - off(t)];  dw[0,c,t] = sum_{b,p} x[b,c,p + off(t)] gs[b,p];
+ *   db = sum gs
+ * Direct fp32 arithmetic, NCDHW, zero padding; any D, H, W >= 1; Cin <= 64; Cout must be 1; Cin D H W, B D H W < 2^31.  dw is reduced in two
+ * stages (per-workgroup partial sums in scratch, added in workgroup order), db likewise; no float atomics: bit-reproducible.
+ *   hav_final_conv_sigmoid_fwd                bias [1] nullable
+ *   hav_final_conv_sigmoid_bwd_scratch_bytes  bytes of `scratch` the backward needs (always > 0; 0 for shapes it refuses)
+ *   hav_final_conv_sigmoid_bwd                vol = the forward's output; each of dx, dw, db nullable (not all three); x may be NULL
+ *                                             without dw, w without dx
+ * NULL pointers / sizes < 1: HAV_EINVAL; Cout != 1, Cin > 64, oversize: HAV_EUNSUP; both before any launch, outputs untouched.
+ * ------------------------------------------------------------------------------------------ */
+int hav_final_conv_sigmoid_fwd(float* vol, const float* x, const float* w, const float* bias, int B, int Cin, int Cout, int D, int H, int W,
+                               void* stream);
+int64_t hav_final_conv_sigmoid_bwd_scratch_bytes(int B, int Cin, int Cout, int D, int H, int W);
+int hav_final_conv_sigmoid_bwd(float* dx, float* dw, float* db, const float* dvol, const float* vol, const float* x, const float* w,
+                               void* scratch, int B, int Cin, int Cout, int D, int H, int W, void* stream);
 
 /* Haar analysis / synthesis of SWGAN_unet's wavelet-domain skip path (model/styleUnet.py HaarTransform / InverseHaarTransform: four
  * upfirdn2d calls each, + cat / + three adds) as one pass each, bit-identical to the four-call sequence.
