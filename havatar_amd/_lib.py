@@ -111,6 +111,16 @@ def lib():
     L.hav_composite_fwd.restype = i32
     L.hav_composite_bwd.argtypes = [vp] * 10 + [i64, i32, i32, i32, vp]
     L.hav_composite_bwd.restype = i32
+    # added within ABI 8 (the version number cannot tell a library built before them): a stale build is named, not an AttributeError
+    for name, args in (("hav_composite_long_fwd", [vp] * 9 + [i64, i32, i32, i32, vp]),
+                       ("hav_composite_long_bwd", [vp] * 10 + [i64, i32, i32, i32, vp]),
+                       ("hav_composite_long_bwd_form", [vp] * 10 + [i64, i32, i32, i32, i32, vp])):
+        try:
+            fn = getattr(L, name)
+        except AttributeError:
+            raise HavatarLibraryError(f"{path} does not export {name}: it was built from older sources; rebuild it with "
+                                      "`python -m havatar_amd.build --force`") from None
+        fn.argtypes, fn.restype = args, i32
     L.hav_resample_depths.argtypes = [vp] * 5 + [i64, i32, i32, vp]
     L.hav_resample_depths.restype = i32
     L.hav_equal_linear_fwd.argtypes = [vp] * 4 + [C.c_float, C.c_float, i32, i32, i32, vp]

@@ -19,6 +19,21 @@ from ..utils.training_util import get_minibatches
 from ..utils.util import UniformBoxWarp_new, get_box_warp_param
 
 
+_warned_wide_sampling = False
+
+
+def _warn_wide_sampling(widest):
+    """once per process: a training step on HIP tensors left the native route because of its sample count"""
+    global _warned_wide_sampling
+    if _warned_wide_sampling:
+        return
+    _warned_wide_sampling = True
+    import warnings
+    warnings.warn("training with %d samples in a pass: the native compositing kernels hold 64, so this step takes the ATen statement of "
+                  "the whole march.  Set HAVATAR_COMPOSITE_LONG=1 to keep it on the native route (up to 128 samples per pass)." % widest,
+                  RuntimeWarning, stacklevel=3)
+
+
 class Trainer(torch.nn.Module):
     def __init__(self, cfg, latent_codes_size=0, freeze_motion=True):
         super().__init__()
@@ -181,10 +196,17 @@ class Trainer(torch.nn.Module):
         # HIP tensors under autograd: the field inputs (skinning + box warp + plane gather + encoding) and the compositing are
         # one kernel each way (hav_field_inputs_*, hav_composite_*); the MLP between them stays on rocBLAS.  No fallback: with
         # HAVATAR_HIP_TRAIN unset or 1 a missing library raises.
-        fused = (ro.is_cuda and ro.dtype == torch.float32 and max(opt.num_coarse, opt.num_coarse // 2 + opt.num_coarse % 2 + opt.num_fine) <= 64
-                 and self.model_coarse.sh_deg == 0 and os.environ.get("HAVATAR_HIP_TRAIN", "1") != "0")
+        # Samples per pass: hav_composite_* holds 64 (a lane per sample), hav_composite_long_* 128 (two per lane); the latter is opt-in
+        # (HAVATAR_COMPOSITE_LONG=1, read here).  Without it a wider sampling takes the ATen statement below, and says so once.
+        widest = max(opt.num_coarse, opt.num_coarse // 2 + opt.num_coarse % 2 + opt.num_fine)
+        fused = (ro.is_cuda and ro.dtype == torch.float32 and self.model_coarse.sh_deg == 0 and os.environ.get("HAVATAR_HIP_TRAIN", "1") != "0")
+        if fused and widest > 64:
+            long_on = os.environ.get("HAVATAR_COMPOSITE_LONG", "0") == "1"
+            if not long_on and 64 < widest <= 128:
+                _warn_wide_sampling(widest)
+            fused = long_on and widest <= 128
         if fused:
-            from ..native.train_ops import composite, field_inputs, field_mlp, field_mlp_eligible
+            from ..native.train_ops import composite, composite_long, field_inputs, field_mlp, field_mlp_eligible
             gw, sw = self.model_coarse.gridwarper, self.headpose_skin_net.gridwarper
             if getattr(self, "_boxes", None) is None:
                 f = lambda t: t.detach().reshape(3).cpu().tolist()
@@ -211,7 +233,9 @@ class Trainer(torch.nn.Module):
                 rf = mc.mlp(X).reshape(B * R, zv.shape[-1], -1).float()      # (bf16 under autocast: the compositing is fp32)
             std = float(opt.radiance_field_noise_std)
             noise = torch.randn(rf.shape[:-1], dtype=rf.dtype, device=rf.device) * std if std > 0.0 else None     # same draw as :56
-            rgb, acc, w, depth = composite(rf, zv.reshape(-1, zv.shape[-1]), rd.reshape(-1, 3), noise, bg, n_sigmoid=3)
+            # a pass of at most 64 samples keeps hav_composite_* whatever the switch says (a 64+16 step has the same bits either way)
+            comp = composite if zv.shape[-1] <= 64 else composite_long
+            rgb, acc, w, depth = comp(rf, zv.reshape(-1, zv.shape[-1]), rd.reshape(-1, 3), noise, bg, n_sigmoid=3)
             return rgb, None, acc, w, depth
 
         def one_pass(zv):

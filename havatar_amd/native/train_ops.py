@@ -208,6 +208,65 @@ def composite(rf, z, rd, noise=None, bg=None, n_sigmoid=3):
     return Composite.apply(rf, z, rd, noise, bg, n_sigmoid)
 
 
+class CompositeLong(Function):
+    """Composite for 1 <= S <= 128 samples per ray (hav_composite_long_*: two adjacent samples per lane).  Same tensors, same maps; the
+    transmittance product is associated as a tree, so results agree with Composite to rounding, not to the bit.  bwd_form names the
+    backward's arrangement (0 = by shape; include/havatar.h::hav_composite_long_bwd_form) for the A/B tool and the tests."""
+
+    @staticmethod
+    @_fwd32
+    def forward(ctx, rf, z, rd, noise, bg, n_sigmoid, bwd_form=0):
+        _need_hip("CompositeLong", rf, z, rd, noise, bg)
+        rf, z, rd = rf.contiguous(), z.contiguous(), rd.contiguous()
+        noise = noise.contiguous() if noise is not None else None
+        bg = bg.contiguous() if bg is not None else None
+        n, S, RW = rf.shape
+        if z.shape != (n, S) or rd.shape != (n, 3) or (noise is not None and noise.shape != (n, S)) or (bg is not None and bg.shape != (n, 3)):
+            raise RuntimeError("CompositeLong: rf [n,S,CH+1], z [n,S], rd [n,3], noise [n,S], bg [n,3]")
+        rgb = torch.empty(n, RW - 1, device=rf.device, dtype=torch.float32)
+        acc, depth = torch.empty(n, device=rf.device), torch.empty(n, device=rf.device)
+        w = torch.empty(n, S, device=rf.device)
+        with torch.cuda.device(rf.device):
+            rc = _lib.lib().hav_composite_long_fwd(_p(rgb), _p(acc), _p(w), _p(depth), _p(rf), _p(z), _p(rd), _p(noise), _p(bg), n, S, RW - 1,
+                                                   int(n_sigmoid), _stream())
+        _lib.check(rc, "hav_composite_long_fwd")
+        ctx.save_for_backward(rf, z, rd, noise, bg)
+        ctx.n_sigmoid, ctx.bwd_form = int(n_sigmoid), int(bwd_form)
+        return rgb, acc, w, depth
+
+    @staticmethod
+    @once_differentiable
+    @_bwd32
+    def backward(ctx, d_rgb, d_acc, d_w, d_depth):
+        rf, z, rd, noise, bg = ctx.saved_tensors
+        n, S, RW = rf.shape
+        d_rf = torch.empty_like(rf)
+        d_rgb = d_rgb.contiguous() if d_rgb is not None else torch.zeros(n, RW - 1, device=rf.device)
+        d_acc, d_w, d_depth = [t.contiguous() if t is not None else None for t in (d_acc, d_w, d_depth)]
+        with torch.cuda.device(rf.device):
+            rc = _lib.lib().hav_composite_long_bwd_form(_p(d_rf), _p(d_rgb), _p(d_acc), _p(d_w), _p(d_depth), _p(rf), _p(z), _p(rd), _p(noise),
+                                                        _p(bg), n, S, RW - 1, ctx.n_sigmoid, ctx.bwd_form, _stream())
+        _lib.check(rc, "hav_composite_long_bwd")
+        from .conv import _trace
+        _trace("CompositeLong.bwd d_rf,d_rgb,rf", d_rf, d_rgb, rf)
+        return d_rf, None, None, None, None, None, None
+
+
+def composite_long(rf, z, rd, noise=None, bg=None, n_sigmoid=3, bwd_form=0):
+    """composite() for up to 128 samples per ray; raises RuntimeError where the library refuses (S > 128)."""
+    return CompositeLong.apply(rf, z, rd, noise, bg, n_sigmoid, bwd_form)
+
+
+def composite_long_eligible(S, rf_like):
+    """what composite_long takes: a HIP float32 radiance field and at most 128 samples per ray"""
+    return bool(rf_like.is_cuda and rf_like.dtype == torch.float32 and 1 <= int(S) <= 128)
+
+
+def composite_long_enabled():
+    """HAVATAR_COMPOSITE_LONG=1 (read at the call): a training step with 65-128 samples per pass stays on the native route"""
+    return os.environ.get("HAVATAR_COMPOSITE_LONG", "0") == "1"
+
+
 def resample_depths(z, weights, num_fine, zeta=None, return_samples=False):
     """z2 [n, ceil(S_c/2)+num_fine] = sort(cat(z[:, ::2], sample_pdf(z_mid, weights[:, 1:-1], num_fine))) -- the statements of
     model/nerf_trainer.py:166-170 + utils/nerf_util.py:76-117 of the reference as one launch (hav_resample_depths).  z, weights

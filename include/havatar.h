@@ -187,6 +187,28 @@ int hav_composite_fwd(float* rgb, float* acc, float* weights, float* depth, cons
 int hav_composite_bwd(float* d_rf, const float* d_rgb, const float* d_acc, const float* d_weights, const float* d_depth,
                       const float* rf, const float* z, const float* rd, const float* noise, const float* bg, int64_t n_rays,
                       int S, int CH, int n_sigmoid, void* stream);
+/* The same compositing for 1 <= S <= 128 samples per ray (added within ABI 8: additive; csrc/hav_composite_long.hip) -- the wider
+ * samplings a training step reaches with HAVATAR_COMPOSITE_LONG=1.  volume_render_radiance_field(act_feat=False), utils/nerf_util.py:28-73:
+ * the repeated last distance (:36-40), sigma = relu(raw + noise) (:54-58), alpha (:59), weights = alpha * cumprod_exclusive(1 - alpha +
+ * 1e-10) (:60, cumprod_exclusive :4-25), the sigmoid on the first n_sigmoid channels (:45-46), rgb / depth / acc maps (:62-68), the
+ * white-background term on the first three channels (:70-71).  Same tensors and null rules as hav_composite_fwd: noise and bg may be NULL.
+ * A lane owns two adjacent samples, so the transmittance product is associated as a tree rather than in cumprod's order (results agree
+ * with hav_composite_fwd to rounding, not to the bit).  S > 128: HAV_EUNSUP before any launch, outputs untouched.  n_rays == 0: 0. */
+int hav_composite_long_fwd(float* rgb, float* acc, float* weights, float* depth, const float* rf, const float* z, const float* rd,
+                           const float* noise, const float* bg, int64_t n_rays, int S, int CH, int n_sigmoid, void* stream);
+/* Its gradient: d_rf [n_rays,S,CH+1] from d_rgb (required) and d_acc / d_weights / d_depth (NULL = zero) -- the adjoint of
+ * utils/nerf_util.py:36-71 (d sigma through relu :58, d alpha through the exclusive product :60 as a suffix sum of G_j w_j, d colour
+ * through the sigmoid :45-46).  A ray's S x (CH+1) block is staged in LDS while it fits one wave's share (S (CH+2) floats + 1 KB <= 64 KB);
+ * larger blocks are walked in memory. */
+int hav_composite_long_bwd(float* d_rf, const float* d_rgb, const float* d_acc, const float* d_weights, const float* d_depth,
+                           const float* rf, const float* z, const float* rd, const float* noise, const float* bg,
+                           int64_t n_rays, int S, int CH, int n_sigmoid, void* stream);
+/* hav_composite_long_bwd with the form of the kernel named instead of picked by shape (the A/B tool and the tests of each form; same
+ * gradient, utils/nerf_util.py:36-71): form 0 = by shape, 1 = staged, one wave per workgroup, 2 = staged, two waves per workgroup
+ * (2 x the block <= 160 KB), 3 = rows walked in memory.  A staged form whose block does not fit: HAV_EUNSUP. */
+int hav_composite_long_bwd_form(float* d_rf, const float* d_rgb, const float* d_acc, const float* d_weights, const float* d_depth,
+                                const float* rf, const float* z, const float* rd, const float* noise, const float* bg,
+                                int64_t n_rays, int S, int CH, int n_sigmoid, int form, void* stream);
 /* Importance resampling between the two passes under autograd (added within ABI 6: additive) -- replaces the ATen chain of
  * model/nerf_trainer.py:166-170 (z_vals_mid, sample_pdf, z_samples.detach(), cat with z_vals[::2], sort) and utils/nerf_util.py:76-117
  * (sample_pdf: +1e-5, sum, cumsum, stratified or linspace u, searchsorted(right), clamped gathers, the 1e-5 denominator floor):
