@@ -114,7 +114,8 @@ def lib():
     # added within ABI 8 (the version number cannot tell a library built before them): a stale build is named, not an AttributeError
     for name, args in (("hav_composite_long_fwd", [vp] * 9 + [i64, i32, i32, i32, vp]),
                        ("hav_composite_long_bwd", [vp] * 10 + [i64, i32, i32, i32, vp]),
-                       ("hav_composite_long_bwd_form", [vp] * 10 + [i64, i32, i32, i32, i32, vp])):
+                       ("hav_composite_long_bwd_form", [vp] * 10 + [i64, i32, i32, i32, i32, vp]),
+                       ("hav_haar_down2", [vp] * 5 + [f32, i32, i32, i32, i32, vp])):
         try:
             fn = getattr(L, name)
         except AttributeError:

@@ -341,6 +341,12 @@ def _fused_haar_enabled():
     return os.environ.get("HAVATAR_FUSED_HAAR", "1") != "0"
 
 
+def _haar_train(x):
+    """HAVATAR_HAAR_TRAIN=1 (read at the call), a float32 HIP tensor, grad mode on: the transforms run as the one-launch autograd nodes of
+    native/train_ops.py (HaarDwt / HaarIdwt / HaarUp2 / HaarDown2) where the shape is eligible.  Unset (the default): today's statements."""
+    return os.environ.get("HAVATAR_HAAR_TRAIN", "0") == "1" and x.is_cuda and x.dtype == torch.float32 and torch.is_grad_enabled()
+
+
 def _haar_bank(mod, ks):
     """[4,2,2] tensor of a transform's four kernels, cached on the module (buffers do not change after construction / .to())."""
     bank = mod.__dict__.get("_bank")
@@ -368,6 +374,11 @@ class HaarTransform(nn.Module):
             out = fused.haar(input, _haar_bank(self, (self.ll, self.lh, self.hl, self.hh)))
             if out is not None:
                 return out
+        if _haar_train(input):
+            from ..native import train_ops           # HIP training, on request: one launch each way (hav_haar_dwt, adjoint hav_haar_idwt)
+            out = train_ops.haar_dwt(input, _haar_bank(self, (self.ll, self.lh, self.hl, self.hh)))
+            if out is not None:
+                return out
         return torch.cat([upfirdn2d(input, k, down=2) for k in (self.ll, self.lh, self.hl, self.hh)], 1)
 
 
@@ -382,6 +393,11 @@ class InverseHaarTransform(nn.Module):
         if input.is_cuda and input.dtype == torch.float32 and not torch.is_grad_enabled() and _fused_haar_enabled():
             from ..native import fused           # HIP inference: four up-sampling filters + three adds as one pass (hav_haar_idwt)
             out = fused.haar(input, _haar_bank(self, (self.ll, self.lh, self.hl, self.hh)), inverse=True)
+            if out is not None:
+                return out
+        if _haar_train(input):
+            from ..native import train_ops           # HIP training, on request: one launch each way (hav_haar_idwt, adjoint hav_haar_dwt)
+            out = train_ops.haar_idwt(input, _haar_bank(self, (self.ll, self.lh, self.hl, self.hh)))
             if out is not None:
                 return out
         parts = input.chunk(4, 1)
@@ -413,9 +429,70 @@ class FromRGB(nn.Module):
 
     def forward(self, input, skip=None):
         if self.downsample:
-            input = self.dwt(self.downsample(self.iwt(input))) if self.use_wt else self.downsample(input)
+            down = None
+            if (self.use_wt and _haar_train(input) and self.downsample.factor == 2 and tuple(self.downsample.pad) == (1, 1)):
+                # HIP training, on request: synthesis, FIR down-sampling and analysis as one launch each way (hav_haar_down2, adjoint hav_haar_up2)
+                from ..native import train_ops
+                down = train_ops.haar_down2(input, _haar_bank(self.iwt, (self.iwt.ll, self.iwt.lh, self.iwt.hl, self.iwt.hh)), self.downsample.kernel,
+                                            _haar_bank(self.dwt, (self.dwt.ll, self.dwt.lh, self.dwt.hl, self.dwt.hh)))
+            input = down if down is not None else (self.dwt(self.downsample(self.iwt(input))) if self.use_wt else self.downsample(input))
         out = self.conv(input)
         return input, (out if skip is None else out + skip)
+
+
+class Discriminator(nn.Module):
+    """Stage-two critic in the Haar-wavelet domain (reference model/styleUnet.py:470-562; same attributes, state_dict keys and
+    construction order, so checkpoints load and a seed gives the same parameters): analysis of the image, then per level a FromRGB
+    (the first without re-sampling, the others dwt(downsample(iwt(.)))) added to a ConvBlock chain, the minibatch standard deviation
+    over groups of `stddev_group` as one more channel at 4 x 4, a 3x3 layer and two linear ones.  c_dim > 0: a four-layer mapping of
+    `flat_pose` whose second-moment-normalised output the prediction is projected on."""
+
+    def __init__(self, size, img_channel=6, channel_multiplier=2, blur_kernel=(1, 3, 3, 1), c_dim=0):
+        super().__init__()
+        ch = _CHANNELS(channel_multiplier)
+        self.dwt = HaarTransform(img_channel)
+        self.from_rgbs, self.convs = nn.ModuleList(), nn.ModuleList()
+        log_size = int(math.log(size, 2)) - 1
+        in_channel = ch[size]
+        for i in range(log_size, 2, -1):
+            out_channel = ch[2 ** (i - 1)]
+            self.from_rgbs.append(FromRGB(in_channel, img_channel, downsample=i != log_size))
+            self.convs.append(ConvBlock(in_channel, out_channel, blur_kernel))
+            in_channel = out_channel
+        self.from_rgbs.append(FromRGB(ch[4], img_channel))
+        self.stddev_group, self.stddev_feat = 4, 1
+        self.final_conv = ConvLayer(in_channel + 1, ch[4], 3)
+        self.final_linear = nn.Sequential(EqualLinear(ch[4] * 4 * 4, ch[4], activation="fused_lrelu"), EqualLinear(ch[4], 1))
+        self.c_dim = c_dim
+        if c_dim > 0:
+            style_dim, lr_mlp = 64, 0.01
+            self.mapping = nn.Sequential(EqualLinear(c_dim, style_dim, lr_mul=lr_mlp, activation="fused_lrelu"),
+                                         *[EqualLinear(style_dim, style_dim, lr_mul=lr_mlp, activation="fused_lrelu") for _ in range(3)])
+
+    def forward(self, input, flat_pose=None):
+        input = self.dwt(input)
+        out = None
+        for from_rgb, conv in zip(self.from_rgbs, self.convs):
+            input, out = from_rgb(input, out)
+            out = conv(out)
+        _, out = self.from_rgbs[-1](input, out)
+
+        # minibatch standard deviation (ATen: a handful of launches on [B,512,4,4]); a batch the group does not divide fails in view()
+        batch, channel, height, width = out.shape
+        group = min(batch, self.stddev_group)
+        stddev = out.view(group, -1, self.stddev_feat, channel // self.stddev_feat, height, width)
+        stddev = torch.sqrt(stddev.var(0, unbiased=False) + 1e-8)
+        stddev = stddev.mean([2, 3, 4], keepdims=True).squeeze(2)
+        out = torch.cat([out, stddev.repeat(group, 1, height, width)], 1)
+
+        out = self.final_linear(self.final_conv(out).view(batch, -1))
+        if self.c_dim > 0:
+            pose_embed = self.normalize_2nd_moment(self.mapping(flat_pose))
+            out = (out * pose_embed).sum(dim=1, keepdim=True) * (1 / math.sqrt(self.c_dim))
+        return out
+
+    def normalize_2nd_moment(self, x, dim=1, eps=1e-8):
+        return x * (x.square().mean(dim=dim, keepdim=True) + eps).rsqrt()
 
 
 class StyledConv(nn.Module):
@@ -499,6 +576,11 @@ class ToRGB(nn.Module):
                 from ..native import fused           # HIP inference: synthesis, x2 FIR up-sampling and analysis as one pass (hav_haar_up2), same bits
                 up = fused.haar_up2(skip, _haar_bank(self.iwt, (self.iwt.ll, self.iwt.lh, self.iwt.hl, self.iwt.hh)), self.upsample.kernel,
                                     _haar_bank(self.dwt, (self.dwt.ll, self.dwt.lh, self.dwt.hl, self.dwt.hh)))
+            if (up is None and self.use_wt and _haar_train(skip) and self.upsample.factor == 2 and tuple(self.upsample.pad) == (2, 1)):
+                # HIP training, on request: the same pass as an autograd node (hav_haar_up2, adjoint hav_haar_down2)
+                from ..native import train_ops
+                up = train_ops.haar_up2(skip, _haar_bank(self.iwt, (self.iwt.ll, self.iwt.lh, self.iwt.hl, self.iwt.hh)), self.upsample.kernel,
+                                        _haar_bank(self.dwt, (self.dwt.ll, self.dwt.lh, self.dwt.hl, self.dwt.hh)))
             skip = up if up is not None else (self.dwt(self.upsample(self.iwt(skip))) if self.use_wt else self.upsample(skip))
         if self.conv._hip_inference(input) and os.environ.get("HAVATAR_FUSED_TORGB", "1") != "0":
             # HIP inference: modulation, the 1x1 convolution, bias and skip add in one pass over the activations (hav_torgb) instead of

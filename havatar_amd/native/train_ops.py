@@ -289,7 +289,9 @@ def resample_depths(z, weights, num_fine, zeta=None, return_samples=False):
 
 class EqualLinearFn(Function):
     """y = F.linear(x, W * scale, bias * lr_mul) for x [B <= 8, in]: one launch forward, one backward (hav_equal_linear_*), instead of the
-    3 + 6-7 ATen launches of the statement (model/styleUnet.py:128-162 of the reference) -- the modulation layer of every ModulatedConv2d."""
+    3 + 6-7 ATen launches of the statement (model/styleUnet.py:128-162 of the reference) -- the modulation layer of every ModulatedConv2d
+    and the discriminator's last layer.  Under create_graph=True the backward states the adjoints with differentiable ATen ops; inside
+    conv2d_gradfix.no_weight_gradients() no weight gradient is formed."""
 
     @staticmethod
     @_fwd32
@@ -310,11 +312,21 @@ class EqualLinearFn(Function):
         return y
 
     @staticmethod
-    @once_differentiable
     @_bwd32
     def backward(ctx, dy):
         x, W = ctx.saved_tensors
         scale, lr_mul, has_bias = ctx.consts
+        if torch.is_grad_enabled():
+            # create_graph=True (R1 through the discriminator's last layer, path length through every modulation layer; reference
+            # utils/styleUnet_util.py:74,92): the three adjoints as differentiable ATen statements, so that the second-order graph exists.
+            # Inside conv2d_gradfix.no_weight_gradients() no weight gradient is formed, as in native/conv.py::_FusedConvBlock
+            from ..model.op import conv2d_gradfix
+            with torch.enable_grad():
+                dx = torch.matmul(dy, W * scale) if ctx.needs_input_grad[0] else None
+                dW = (torch.matmul(dy.t(), x) * scale if (ctx.needs_input_grad[1] and not conv2d_gradfix.weight_gradients_disabled)
+                      else None)
+                db = dy.sum(0) * lr_mul if (has_bias and ctx.needs_input_grad[2]) else None
+            return dx, dW, db, None, None
         dy = dy.contiguous()
         B, n_in = x.shape
         n_out = W.shape[0]
@@ -336,7 +348,8 @@ def equal_linear_eligible(x, W, bias):
 
 
 def equal_linear(x, W, bias, scale, lr_mul):
-    return EqualLinearFn.apply(x, W, bias, scale, lr_mul)
+    # (contiguous OUTSIDE the node: inside, where grad mode is off, a copy would be saved detached and cut the create_graph branch's graph)
+    return EqualLinearFn.apply(x.contiguous(), W.contiguous(), bias, scale, lr_mul)
 
 
 class Upsample3d2x(Function):
@@ -703,3 +716,200 @@ class Demod(Function):
 def demod(s, W, scale, eps=1e-8):
     """s [B,Cin] (differentiable), W [Cout,Cin,k,k] raw parameter -> d [B,Cout]."""
     return Demod.apply(s, W, scale, eps)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# The wavelet nodes of stage two under autograd (HAVATAR_HAAR_TRAIN=1).  All four maps are linear, so each backward is the PARTNER node's
+# forward, called through its apply(): the graph stays differentiable to any order with no ATen restatement.  Which bank the adjoint
+# takes follows from the kernels' definitions (include/havatar.h; upfirdn2d applies its kernel flipped):
+#   dwt_k   : out_band[y, x]    = sum_{i,j} in[2y + i, 2x + j] k_band[1 - i, 1 - j]
+#   idwt_k  : out[2y + i, 2x + j] = sum_band in_band[y, x] k_band[i, j]
+# so <dwt_k x, g> = sum in[2y+i, 2x+j] g_band[y, x] k_band[1-i, 1-j] = <x, idwt_flip(k) g>, and likewise idwt_k^T = dwt_flip(k), with
+# flip = both axes of every 2x2 kernel reversed (for the Haar banks: flip(ll, lh, hl, hh) = (ll, -lh, -hl, hh), the other module's bank).
+# The FIR stages: up_f (up 2, pad (2, 1)) has out[Y] = sum_y x[y] f[1 + Y - 2y] and down_f (down 2, pad (1, 1)) has out[y] = sum_Y
+# x[Y] f[2 + 2y - Y] per axis, so up_f^T = down_flip(f) and down_f^T = up_flip(f).  Composed:
+#   up2(ki, f, kd)^T          = down2(flip kd, flip f, flip ki, 1) = down2(flip kd, flip f / 4, flip ki, 4)
+#   down2(ki, f, kd, s)^T     = up2(flip kd, s flip f, flip ki)
+# (the / 4 and * 4 are exact; they keep the decimating FIR at Downsample's gain-free size, whatever order of differentiation).
+# tests/test_haar_train_gpu.py asserts every one of these through <A x, y> = <x, A^T y> in fp64.
+_FLIPS = {}
+
+
+def _flipped(k, mul=1.0):
+    """k [..., m, m] with the last two axes reversed, times mul; cached per tensor (banks are module buffers: a handful per network).  A
+    miss while a stream is capturing is computed inside the capture and not kept (its memory belongs to the graph's pool); the warm-up
+    that precedes a capture fills the cache, so a captured step reads the kept tensors"""
+    slot = (k.data_ptr(), k._version, str(k.device), tuple(k.shape), tuple(k.stride()), float(mul))
+    hit = _FLIPS.get(slot)
+    if hit is not None:          # (same memory, same layout, same version: the same values, whichever tensor object names them)
+        return hit[1]
+    with torch.no_grad():
+        out = k.flip(-2, -1)
+        out = (out * mul if mul != 1.0 else out).contiguous()
+    if not torch.cuda.is_current_stream_capturing():
+        if len(_FLIPS) >= 256:
+            _FLIPS.clear()
+        _FLIPS[slot] = (k, out)          # (the source is kept alive: its memory cannot be handed to another tensor while the entry stands)
+    return out
+
+
+def haar_enabled():
+    """HAVATAR_HAAR_TRAIN=1 (read at the call): the wavelet transforms of both stage-two networks run as one-launch autograd nodes"""
+    return os.environ.get("HAVATAR_HAAR_TRAIN", "0") == "1"
+
+
+def _haar_tensor(x):
+    """a 4-D HIP float32 tensor whose planes start on 16-byte boundaries once contiguous (the existing kernels' float4 accesses)"""
+    return bool(x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and (not x.is_contiguous() or x.data_ptr() % 16 == 0))
+
+
+def haar_dwt_eligible(x):
+    """[B,C,H,W] HIP float32 with H even and W % 8 == 0 (hav_haar_dwt; its adjoint hav_haar_idwt then sees W/2 % 4 == 0)"""
+    return _haar_tensor(x) and x.shape[2] >= 2 and x.shape[2] % 2 == 0 and x.shape[3] >= 8 and x.shape[3] % 8 == 0 and x.shape[1] >= 1
+
+
+def haar_idwt_eligible(x):
+    """[B,4C,H,W] HIP float32 with W % 4 == 0 (hav_haar_idwt; its adjoint hav_haar_dwt then sees 2H even and 2W % 8 == 0)"""
+    return _haar_tensor(x) and x.shape[1] >= 4 and x.shape[1] % 4 == 0 and x.shape[2] >= 1 and x.shape[3] >= 4 and x.shape[3] % 4 == 0
+
+
+def haar_up2_eligible(x, fir):
+    """[B,4C,H,W] HIP float32 with W even and a 4x4 FIR (hav_haar_up2; its adjoint hav_haar_down2 sees 2H, 2W: even)"""
+    return (_haar_tensor(x) and x.shape[1] >= 4 and x.shape[1] % 4 == 0 and x.shape[2] >= 1 and x.shape[3] >= 2 and x.shape[3] % 2 == 0
+            and tuple(fir.shape) == (4, 4))
+
+
+def haar_down2_eligible(x, fir):
+    """[B,4C,H,W] HIP float32 with H and W even and a 4x4 FIR (hav_haar_down2), and W % 4 == 0 so that its adjoint hav_haar_up2 sees an
+    even width"""
+    return (_haar_tensor(x) and x.shape[1] >= 4 and x.shape[1] % 4 == 0 and x.shape[2] >= 2 and x.shape[2] % 2 == 0 and x.shape[3] >= 4
+            and x.shape[3] % 4 == 0 and tuple(fir.shape) == (4, 4))
+
+
+def haar_down2_raw(x, ki4, fir, kd4, scale=1.0):
+    """scale * dwt(upfirdn2d(iwt(x), fir, down 2, pad (1, 1))) as one launch (hav_haar_down2), no autograd: x [B,4C,H,W] -> [B,4C,H/2,W/2].
+    Raises on anything but HIP float32 tensors; returns None where the library refuses the shape (odd H or W)."""
+    _need_hip("haar_down2", x, ki4, fir, kd4)
+    if x.dim() != 4 or x.shape[1] % 4 or x.shape[1] < 4 or tuple(fir.shape) != (4, 4) or ki4.numel() != 16 or kd4.numel() != 16:
+        return None
+    B, Cc, H, W = x.shape
+    if H < 1 or W < 1 or H % 2 or W % 2:
+        return None
+    x, ki4, fir, kd4 = x.contiguous(), ki4.contiguous(), fir.contiguous(), kd4.contiguous()
+    out = torch.empty(B, Cc, H // 2, W // 2, device=x.device, dtype=torch.float32)
+    with torch.cuda.device(x.device):
+        rc = _lib.lib().hav_haar_down2(_p(out), _p(x), _p(ki4), _p(fir), _p(kd4), float(scale), B, Cc // 4, H, W, _stream())
+    if rc == -2:          # HAV_EUNSUP
+        return None
+    _lib.check(rc, "hav_haar_down2")
+    return out
+
+
+def _haar_call(name, x, k4, inverse):
+    from . import fused
+    out = fused.haar(x, k4, inverse=inverse)
+    if out is None:
+        raise RuntimeError(name + ": shape not taken (check *_eligible first)")
+    return out
+
+
+class HaarDwt(Function):
+    """HaarTransform as one launch under autograd (hav_haar_dwt): x [B,C,H,W] -> [B,4C,H/2,W/2]; backward = HaarIdwt with the flipped bank."""
+
+    @staticmethod
+    @_fwd32
+    def forward(ctx, x, k4):
+        _need_hip("HaarDwt", x, k4)
+        ctx.save_for_backward(k4)
+        return _haar_call("HaarDwt", x, k4, False)
+
+    @staticmethod
+    @_bwd32
+    def backward(ctx, g):
+        k4, = ctx.saved_tensors
+        return (HaarIdwt.apply(g.contiguous(), _flipped(k4)) if ctx.needs_input_grad[0] else None), None
+
+
+class HaarIdwt(Function):
+    """InverseHaarTransform as one launch under autograd (hav_haar_idwt): x [B,4C,H,W] -> [B,C,2H,2W]; backward = HaarDwt with the flipped bank."""
+
+    @staticmethod
+    @_fwd32
+    def forward(ctx, x, k4):
+        _need_hip("HaarIdwt", x, k4)
+        ctx.save_for_backward(k4)
+        return _haar_call("HaarIdwt", x, k4, True)
+
+    @staticmethod
+    @_bwd32
+    def backward(ctx, g):
+        k4, = ctx.saved_tensors
+        return (HaarDwt.apply(g.contiguous(), _flipped(k4)) if ctx.needs_input_grad[0] else None), None
+
+
+class HaarUp2(Function):
+    """ToRGB's skip path dwt(upsample(iwt(x))) as one launch under autograd (hav_haar_up2): [B,4C,H,W] -> [B,4C,2H,2W]; backward =
+    HaarDown2 with the flipped banks, FIR / 4 and scale 4."""
+
+    @staticmethod
+    @_fwd32
+    def forward(ctx, x, ki4, fir, kd4):
+        from . import fused
+        _need_hip("HaarUp2", x, ki4, fir, kd4)
+        out = fused.haar_up2(x, ki4, fir, kd4)
+        if out is None:
+            raise RuntimeError("HaarUp2: shape not taken (check haar_up2_eligible first)")
+        ctx.save_for_backward(ki4, fir, kd4)
+        return out
+
+    @staticmethod
+    @_bwd32
+    def backward(ctx, g):
+        ki4, fir, kd4 = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        return HaarDown2.apply(g.contiguous(), _flipped(kd4), _flipped(fir, 0.25), _flipped(ki4), 4.0), None, None, None
+
+
+class HaarDown2(Function):
+    """FromRGB's wavelet-domain down-sampling scale * dwt(downsample(iwt(x))) as one launch under autograd (hav_haar_down2): [B,4C,H,W] ->
+    [B,4C,H/2,W/2]; backward = HaarUp2 with the flipped banks and scale * FIR."""
+
+    @staticmethod
+    @_fwd32
+    def forward(ctx, x, ki4, fir, kd4, scale):
+        out = haar_down2_raw(x, ki4, fir, kd4, scale)
+        if out is None:
+            raise RuntimeError("HaarDown2: shape not taken (check haar_down2_eligible first)")
+        ctx.save_for_backward(ki4, fir, kd4)
+        ctx.scale = float(scale)
+        return out
+
+    @staticmethod
+    @_bwd32
+    def backward(ctx, g):
+        ki4, fir, kd4 = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        return HaarUp2.apply(g.contiguous(), _flipped(kd4), _flipped(fir, ctx.scale), _flipped(ki4)), None, None, None, None
+
+
+def haar_dwt(x, k4):
+    """HaarDwt where the shape is eligible, else None (the caller keeps its statement); anything but HIP float32 tensors raises"""
+    _need_hip("haar_dwt", x, k4)
+    return HaarDwt.apply(x.contiguous(), k4) if haar_dwt_eligible(x) else None
+
+
+def haar_idwt(x, k4):
+    _need_hip("haar_idwt", x, k4)
+    return HaarIdwt.apply(x.contiguous(), k4) if haar_idwt_eligible(x) else None
+
+
+def haar_up2(x, ki4, fir, kd4):
+    _need_hip("haar_up2", x, ki4, fir, kd4)
+    return HaarUp2.apply(x.contiguous(), ki4, fir, kd4) if haar_up2_eligible(x, fir) else None
+
+
+def haar_down2(x, ki4, fir, kd4, scale=1.0):
+    _need_hip("haar_down2", x, ki4, fir, kd4)
+    return HaarDown2.apply(x.contiguous(), ki4, fir, kd4, float(scale)) if haar_down2_eligible(x, fir) else None

@@ -422,6 +422,18 @@ int hav_haar_idwt(float* out, const float* in, const float* k4x2x2, int B, int C
  * ki4x2x2 / kd4x2x2: the synthesis / analysis kernels as the two calls above receive them; fir4x4: Upsample's kernel (gain folded in).  W even. */
 int hav_haar_up2(float* out, const float* in, const float* ki4x2x2, const float* fir4x4, const float* kd4x2x2, int B, int C, int H, int W,
                  void* stream);
+/* Its down-sampling twin (csrc/hav_stage2.hip; added within ABI 8: additive) -- replaces FromRGB(use_wt=True)'s
+ * `input = self.dwt(self.downsample(self.iwt(input)))` (model/styleUnet.py:453-458 of the reference: InverseHaarTransform -> Downsample (4x4
+ * FIR, down 2, pad (1, 1)) -> HaarTransform; three upfirdn2d-based stages, nine FIR launches) by one pass:
+ *   out [B,4C,H/2,W/2] = scale * dwt(upfirdn2d(iwt(in [B,4C,H,W]), fir, down 2, pad (1, 1)))
+ * channel = band*C + c; ki4x2x2 / kd4x2x2 / fir4x4 as hav_haar_up2 takes them (Downsample's kernel carries no gain).  At scale 1 the result is
+ * bit-identical to hav_haar_idwt -> hav_upfirdn2d -> hav_haar_dwt; a power-of-two scale multiplies it exactly.  With the three banks flipped
+ * and scale 4 it is the adjoint of hav_haar_up2 (native/train_ops.py::HaarUp2).
+ * Eligible: H even, W even (any B, C >= 1; fewer than 2^31 workgroups of 256 threads, a thread = 4 output columns of one plane row).
+ * W % 8 == 0 with 16-byte aligned tensors takes 16-byte loads and stores, anything else eligible 4-byte ones.  NULL / sizes < 1: HAV_EINVAL;
+ * odd H or W, oversize: HAV_EUNSUP; both before any launch, `out` untouched (the caller keeps its three-stage statement). */
+int hav_haar_down2(float* out, const float* in, const float* ki4x2x2, const float* fir4x4, const float* kd4x2x2, float scale,
+                   int B, int C, int H, int W, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Trilinear x2 up-sampling of a [N,C,D,H,W] float32 volume and its adjoint -- nn.Upsample(scale_factor=2, mode='trilinear',
