@@ -115,13 +115,17 @@ def lib():
     for name, args in (("hav_composite_long_fwd", [vp] * 9 + [i64, i32, i32, i32, vp]),
                        ("hav_composite_long_bwd", [vp] * 10 + [i64, i32, i32, i32, vp]),
                        ("hav_composite_long_bwd_form", [vp] * 10 + [i64, i32, i32, i32, i32, vp]),
-                       ("hav_haar_down2", [vp] * 5 + [f32, i32, i32, i32, i32, vp])):
+                       ("hav_haar_down2", [vp] * 5 + [f32, i32, i32, i32, i32, vp]),
+                       ("hav_s2_image_loss_blocks", [i32, i32]),
+                       ("hav_s2_image_loss_fwd", [vp, vp, vp] + [i64] * 4 + [vp] + [i64] * 3 + [vp] * 4 + [i32, i32, i32, vp]),
+                       ("hav_s2_image_loss_bwd", [vp, vp] + [i64] * 4 + [vp, vp, vp] + [i64] * 4 + [vp] + [i64] * 3 + [vp] * 4
+                        + [i32, i32, i32, i32, vp])):
         try:
             fn = getattr(L, name)
         except AttributeError:
             raise HavatarLibraryError(f"{path} does not export {name}: it was built from older sources; rebuild it with "
                                       "`python -m havatar_amd.build --force`") from None
-        fn.argtypes, fn.restype = args, i32
+        fn.argtypes, fn.restype = args, (i64 if name.endswith("_blocks") else i32)
     L.hav_resample_depths.argtypes = [vp] * 5 + [i64, i32, i32, vp]
     L.hav_resample_depths.restype = i32
     L.hav_equal_linear_fwd.argtypes = [vp] * 4 + [C.c_float, C.c_float, i32, i32, i32, vp]

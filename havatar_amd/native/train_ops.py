@@ -913,3 +913,106 @@ def haar_up2(x, ki4, fir, kd4):
 def haar_down2(x, ki4, fir, kd4, scale=1.0):
     _need_hip("haar_down2", x, ki4, fir, kd4)
     return HaarDown2.apply(x.contiguous(), ki4, fir, kd4, float(scale)) if haar_down2_eligible(x, fir) else None
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# The image-space losses of the stage-two joint step (hav_s2_image_loss_*: csrc/hav_s2_loss.hip; reference train_avatarHD.py:246-283)
+# ---------------------------------------------------------------------------------------------------------------------------------------
+def s2_loss_enabled():
+    """harness/train_hd.py::joint_step takes Stage2ImageLoss for its image-space losses where the tensors are eligible (the default: the node is
+    faster than the statement at both measured sizes); HAVATAR_S2_LOSS=0 selects the ATen statement.  Read at the call."""
+    return os.environ.get("HAVATAR_S2_LOSS", "1") != "0"
+
+
+def stage2_image_loss_statement(render, mask, gt_lr_img, fake_img, gt_hr_img, gt_lr_mask, rgb_loss="mse"):
+    """The reference's statements (train_avatarHD.py:246-247, :251, :268, :282-283) ->
+    (rgb_loss, hr_l1, mask_bce, lr_mse.detach(), sr_mse.detach()); mask_bce is unweighted."""
+    F = torch.nn.functional
+    G = gt_lr_img.shape[-1]
+    lr_img = F.interpolate(render[:, :3], size=(G, G), mode="bilinear", align_corners=True)
+    rgb = (F.mse_loss if rgb_loss == "mse" else F.l1_loss)(lr_img, gt_lr_img)
+    bce = F.binary_cross_entropy(mask.clip(1e-3, 1.0 - 1e-3), gt_lr_mask)
+    hr_l1 = F.l1_loss(fake_img, gt_hr_img)
+    return rgb, hr_l1, bce, F.mse_loss(lr_img, gt_lr_img).detach(), F.mse_loss(fake_img, gt_hr_img).detach()
+
+
+def stage2_image_loss_eligible(render, mask, gt_lr_img, fake_img, gt_hr_img, gt_lr_mask):
+    """Float32 HIP tensors, render [B,C>=3,r,r] (any strides), mask / gt_lr_mask [B,1,r,r], the three images [B,3,G,G], 2 <= r <= G,
+    grad mode on.  (No cap on G / r: the backward's gather walks (2 (G - 1) / (r - 1) + 4)^2 pixels per low-resolution element, serially --
+    measured at G / r = 4; see the cost note in csrc/hav_s2_loss.hip before using it at ratios far above that.)"""
+    ts = (render, mask, gt_lr_img, fake_img, gt_hr_img, gt_lr_mask)
+    if not all(t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 for t in ts):
+        return False
+    if not torch.is_grad_enabled():
+        return False
+    B, Cc, r, r2 = render.shape
+    G = gt_lr_img.shape[-1]
+    if Cc < 3 or r != r2 or not (2 <= r <= G) or B < 1:
+        return False
+    return (tuple(mask.shape) == tuple(gt_lr_mask.shape) == (B, 1, r, r)
+            and tuple(gt_lr_img.shape) == tuple(fake_img.shape) == tuple(gt_hr_img.shape) == (B, 3, G, G))
+
+
+class Stage2ImageLoss(Function):
+    """(rgb3 [B,3,r,r] = render[:, :3] as a strided view, mask, gt_lr_img, fake_img, gt_hr_img, gt_lr_mask, rgb_mse) ->
+    (rgb_loss, hr_l1, mask_bce, lr_mse, sr_mse): one pass and a one-workgroup reduction forward, one pass backward, no float atomics either
+    way.  lr_img is never written.  First order only.  The narrow view keeps the other C - 3 channels out of the node: autograd's own slice
+    backward pads them with exact zeros."""
+
+    @staticmethod
+    @_fwd32
+    def forward(ctx, rgb3, mask, gt_lr_img, fake_img, gt_hr_img, gt_lr_mask, rgb_mse):
+        _need_hip("Stage2ImageLoss", rgb3, mask, gt_lr_img, fake_img, gt_hr_img, gt_lr_mask)
+        gt_lr_img, fake_img, gt_hr_img, gt_lr_mask = (t.contiguous() for t in (gt_lr_img, fake_img, gt_hr_img, gt_lr_mask))
+        B, _, r, _ = rgb3.shape
+        G = gt_lr_img.shape[-1]
+        L = _lib.lib()
+        out = torch.empty(5, device=rgb3.device, dtype=torch.float32)
+        partials = torch.empty(5 * int(L.hav_s2_image_loss_blocks(B, G)), device=rgb3.device, dtype=torch.float64)
+        rs, ms = rgb3.stride(), mask.stride()
+        with torch.cuda.device(rgb3.device):
+            _lib.check(L.hav_s2_image_loss_fwd(_p(out), _p(partials), _p(rgb3), rs[0], rs[1], rs[2], rs[3], _p(mask), ms[0], ms[2], ms[3],
+                                               _p(gt_lr_img), _p(fake_img), _p(gt_hr_img), _p(gt_lr_mask), B, r, G, _stream()),
+                       "hav_s2_image_loss_fwd")
+        ctx.save_for_backward(rgb3, mask, gt_lr_img, fake_img, gt_hr_img, gt_lr_mask)
+        ctx.rgb_mse = bool(rgb_mse)
+        rgb, hr_l1, bce, lr_mse, sr_mse = out[1 if rgb_mse else 0], out[2], out[4], out[1], out[3]
+        ctx.mark_non_differentiable(lr_mse, sr_mse)
+        return rgb, hr_l1, bce, lr_mse, sr_mse
+
+    @staticmethod
+    @once_differentiable
+    @_bwd32
+    def backward(ctx, g_rgb, g_hr, g_bce, _g_lr_mse, _g_sr_mse):
+        rgb3, mask, gt_lr_img, fake_img, gt_hr_img, gt_lr_mask = ctx.saved_tensors
+        need_r, need_m, need_f = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[3]
+        if not (need_r or need_m or need_f):
+            return (None,) * 7
+        B, _, r, _ = rgb3.shape
+        G = gt_lr_img.shape[-1]
+        zero = rgb3.new_zeros(())
+        gup = torch.stack([(g if g is not None else zero).reshape(()).float() for g in (g_rgb, g_hr, g_bce)])
+        # grad_render in the layout the render arrives in ([B,r,r,3] permuted): the slice backward copies it into the C-channel gradient
+        d_r = torch.empty(B, r, r, 3, device=rgb3.device, dtype=torch.float32).permute(0, 3, 1, 2) if need_r else None
+        d_m = torch.empty(B, 1, r, r, device=rgb3.device, dtype=torch.float32) if need_m else None
+        d_f = torch.empty_like(fake_img) if need_f else None
+        rs, ms = rgb3.stride(), mask.stride()
+        gs = d_r.stride() if need_r else (0, 0, 0, 0)
+        with torch.cuda.device(rgb3.device):
+            _lib.check(_lib.lib().hav_s2_image_loss_bwd(_p(d_f), _p(d_r), gs[0], gs[1], gs[2], gs[3], _p(d_m), _p(gup), _p(rgb3), rs[0], rs[1],
+                                                        rs[2], rs[3], _p(mask), ms[0], ms[2], ms[3], _p(gt_lr_img), _p(fake_img), _p(gt_hr_img),
+                                                        _p(gt_lr_mask), int(ctx.rgb_mse), B, r, G, _stream()), "hav_s2_image_loss_bwd")
+        return d_r, d_m, None, d_f, None, None, None
+
+
+def stage2_image_loss(render, mask, gt_lr_img, fake_img, gt_hr_img, gt_lr_mask, rgb_loss="mse", native=None):
+    """The five image-space scalars of the joint step.  native=None: Stage2ImageLoss where the tensors are eligible unless HAVATAR_S2_LOSS=0,
+    the ATen statement otherwise; native=True insists on the node (anything it does not take raises), native=False on the statement."""
+    if native is None:
+        native = s2_loss_enabled() and stage2_image_loss_eligible(render, mask, gt_lr_img, fake_img, gt_hr_img, gt_lr_mask)
+    if not native:
+        return stage2_image_loss_statement(render, mask, gt_lr_img, fake_img, gt_hr_img, gt_lr_mask, rgb_loss)
+    _need_hip("stage2_image_loss", render, mask, gt_lr_img, fake_img, gt_hr_img, gt_lr_mask)
+    if not stage2_image_loss_eligible(render, mask, gt_lr_img, fake_img, gt_hr_img, gt_lr_mask):
+        raise RuntimeError("stage2_image_loss: not eligible (float32 HIP tensors, 2 <= r <= G, grad mode on)")
+    return Stage2ImageLoss.apply(render[:, :3], mask, gt_lr_img, fake_img, gt_hr_img, gt_lr_mask, rgb_loss == "mse")

@@ -435,6 +435,28 @@ int hav_haar_up2(float* out, const float* in, const float* ki4x2x2, const float*
 int hav_haar_down2(float* out, const float* in, const float* ki4x2x2, const float* fir4x4, const float* kd4x2x2, float scale,
                    int B, int C, int H, int W, void* stream);
 
+/* The image-space losses of the stage-two joint step (csrc/hav_s2_loss.hip; added within ABI 8: additive) -- the reference's
+ * train_avatarHD.py:246-247 (bilinear up-sampling of render[:, :3] to G x G, align_corners, and its l1 / mse against gt_lr_img), :251 (binary
+ * cross entropy of mask.clip(1e-3, 1 - 1e-3)), :268 (l1 of the generator's image) and :282-283 (the two mse behind the PSNRs) as one pass
+ * forward and one backward, without float atomics: the same inputs give the same bits on every launch.
+ *   render [B,C>=3,r,r] and mask [B,1,r,r] are read through ELEMENT strides (b, c, y, x / b, y, x): permuted views of [B,r,r,C] are taken as
+ *   they are; gt_lr, fake, gt_hr [B,3,G,G] and gt_mask [B,1,r,r] are contiguous.
+ *   fwd: out5 = { mean |lr - gt_lr|, mean (lr - gt_lr)^2, mean |fake - gt_hr|, mean (fake - gt_hr)^2, mean bce }; `partials` holds
+ *        5 * hav_s2_image_loss_blocks(B, G) doubles (the workgroups' sums, added in a fixed order by a second, one-workgroup kernel).
+ *   bwd: gup3 = the upstream gradients of { the colour loss, the l1 of fake, the cross entropy } on the device; rgb_mse selects which colour
+ *        loss gup3[0] belongs to (0: l1, 1: mse).  gfake [B,3,G,G] and gmask [B,1,r,r] contiguous, grender [B,3,r,r] through element strides;
+ *        any of the three may be NULL (not wanted).  grender is a gather over the high-resolution pixels whose taps include the element.
+ * Eligible: 2 <= r <= G.  NULL / sizes < 1: HAV_EINVAL; r < 2, r > G, oversize: HAV_EUNSUP; both before any launch.  G % 4 == 0 with 16-byte
+ * aligned contiguous tensors takes 16-byte accesses, anything else 4-byte ones.  No allocation, no synchronisation: capturable. */
+int64_t hav_s2_image_loss_blocks(int B, int G);
+int hav_s2_image_loss_fwd(float* out5, double* partials, const float* render, int64_t rsb, int64_t rsc, int64_t rsy, int64_t rsx,
+                          const float* mask, int64_t msb, int64_t msy, int64_t msx, const float* gt_lr, const float* fake,
+                          const float* gt_hr, const float* gt_mask, int B, int r, int G, void* stream);
+int hav_s2_image_loss_bwd(float* gfake, float* grender, int64_t gsb, int64_t gsc, int64_t gsy, int64_t gsx, float* gmask,
+                          const float* gup3, const float* render, int64_t rsb, int64_t rsc, int64_t rsy, int64_t rsx,
+                          const float* mask, int64_t msb, int64_t msy, int64_t msx, const float* gt_lr, const float* fake,
+                          const float* gt_hr, const float* gt_mask, int rgb_mse, int B, int r, int G, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Trilinear x2 up-sampling of a [N,C,D,H,W] float32 volume and its adjoint -- nn.Upsample(scale_factor=2, mode='trilinear',
  * align_corners=False), the first stage of every UpConv3DBlock of the skinning-volume decoder
