@@ -119,7 +119,11 @@ def lib():
                        ("hav_s2_image_loss_blocks", [i32, i32]),
                        ("hav_s2_image_loss_fwd", [vp, vp, vp] + [i64] * 4 + [vp] + [i64] * 3 + [vp] * 4 + [i32, i32, i32, vp]),
                        ("hav_s2_image_loss_bwd", [vp, vp] + [i64] * 4 + [vp, vp, vp] + [i64] * 4 + [vp] + [i64] * 3 + [vp] * 4
-                        + [i32, i32, i32, i32, vp])):
+                        + [i32, i32, i32, i32, vp]),
+                       ("hav_lpips_head_blocks", [i32] * 4),
+                       ("hav_lpips_head_fwd", [vp] * 5 + [i32] * 4 + [vp]),
+                       ("hav_lpips_head_bwd", [vp] * 6 + [i32] * 4 + [vp]),
+                       ("hav_relu_mask_bwd", [vp] * 4 + [i32, i32, i64, vp])):
         try:
             fn = getattr(L, name)
         except AttributeError:

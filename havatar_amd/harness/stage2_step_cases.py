@@ -82,7 +82,7 @@ def _changed(module, before):
     return sum((p.grad is not None) and (b is None or not torch.equal(p.grad, b)) for p, b in zip(module.parameters(), before))
 
 
-def run_iteration(i, batch, nets, optims, cfg, su_args, util, out, tag, records="all"):
+def run_iteration(i, batch, nets, optims, cfg, su_args, util, out, tag, records="all", percep=None):
     """one joint_step with the records taken at its probe points.  A backward leaves the gradients of the modules it does not reach as they
     were (None at first, the previous backward's afterwards): `*_touched_*` counts the parameters whose .grad it changed."""
     snap = {}
@@ -110,18 +110,19 @@ def run_iteration(i, batch, nets, optims, cfg, su_args, util, out, tag, records=
         elif name == "ema" and records == "all":
             out[tag + "_g_ema_sums"] = _sums(nets["g_ema"])
 
-    s = train_hd.joint_step(i, batch, nets, optims, cfg, su_args, None, util=util, probe=probe)
-    for k in SCALARS:
+    s = train_hd.joint_step(i, batch, nets, optims, cfg, su_args, percep, util=util, probe=probe)
+    for k in SCALARS + (("percep_loss",) if percep is not None else ()):
         out["%s_scalar_%s" % (tag, k)] = np.array(s[k])
     return s
 
 
 def run(Trainer, SWGAN_unet, Discriminator, util, split, device="cpu", dtype=torch.float32, iterations=(0, 1), out=None, prefix="", records="all",
-        pinned=False):
+        pinned=False, percep=None):
     """Every iteration starts from the freshly built state and the same seeds (iteration 1 is the step without R1, not the step after
     iteration 0: one Adam update with beta1 = 0 moves every weight by lr * sign(gradient), which turns the rounding noise of the small
     gradients into full-size differences between any two float32 implementations).  pinned: every random number the step consumes is the
-    same on every device (comparisons between devices): latents drawn on the host, the generator's noise strengths zeroed."""
+    same on every device (comparisons between devices): latents drawn on the host, the generator's noise strengths zeroed.  percep: a callable
+    (device, dtype) -> the LPIPS module of the step's 0.1 * LPIPS term (None: no such term, as the fixture was recorded)."""
     out = {} if out is None else out
     for i in iterations:
         if pinned:
@@ -131,5 +132,6 @@ def run(Trainer, SWGAN_unet, Discriminator, util, split, device="cpu", dtype=tor
             out["names_" + n] = np.array([k for k, _ in nets[n].named_parameters()])
         random.seed(11)
         torch.manual_seed(123)
-        run_iteration(i, batch, nets, optims, cfg, su_args, util, out, "%si%d" % (prefix, i), records)
+        run_iteration(i, batch, nets, optims, cfg, su_args, util, out, "%si%d" % (prefix, i), records,
+                      percep=None if percep is None else percep(device, dtype))
     return out

@@ -7,7 +7,8 @@ Same flags, loss formula, optimiser / learning-rate schedule and checkpoint keys
 of the path (the fused HIP kernel is forward-only), while the encoders' custom ops are the HIP kernels with their
 first/second-order autograd.  Validation frames are rendered through the fused kernel (no-grad).
 LPIPS (patch_rgb) needs the `lpips` package and its VGG weights; when they are absent the harness refuses to start unless
-`--percep none` is given, which drops that one term and says so.
+`--percep none` is given, which drops that one term and says so.  `--percep native --percep-vgg PATH --percep-lin PATH` takes the term from
+this package's own module (model/lpips.py: the same function on this library's kernels, no `lpips` / torchvision import).
 """
 import argparse
 import datetime
@@ -252,7 +253,11 @@ def parse_args(argv=None):
     p.add_argument("--datadir", type=str, required=True)
     p.add_argument("--config", type=str, default="config/singleview_512_base.yml", help="Path to (.yml) config file.")
     p.add_argument("--ckpt", type=str, default="", help="Path to load saved checkpoint from.")
-    p.add_argument("--percep", type=str, default="lpips", choices=["lpips", "none"], help="'none' drops the LPIPS patch term (no lpips package / weights)")
+    p.add_argument("--percep", type=str, default="lpips", choices=["lpips", "native", "none"],
+                   help="'native': this package's LPIPS-VGG module (model/lpips.py) on its own kernels; 'none' drops the LPIPS patch term "
+                        "(no lpips package / weights)")
+    p.add_argument("--percep-vgg", type=str, default="", help="--percep native: torchvision VGG16 weights (vgg16-*.pth)")
+    p.add_argument("--percep-lin", type=str, default="", help="--percep native: the lpips package's linear layers (weights/v0.1/vgg.pth)")
     p.add_argument("--max-steps", type=int, default=0, help="stop after this many optimisation steps (0 = experiment.train_iters)")
     return p.parse_args(argv)
 
@@ -273,6 +278,9 @@ def main(argv=None, device=None):
         except ImportError as e:
             raise RuntimeError("experiment.patch_rgb needs the `lpips` package (VGG weights); install it or pass --percep none") from e
         percep_loss_fn = lpips.LPIPS(net="vgg").to(device)
+    elif cfg.experiment.patch_rgb and args.percep == "native":
+        from ..model.lpips import build_for_harness
+        percep_loss_fn = build_for_harness(args.percep_vgg, args.percep_lin, device)
     elif cfg.experiment.patch_rgb:
         print("[train] --percep none: the 0.05 * LPIPS(patch) term of the reference loss is dropped")
     rgb_loss_func = F.mse_loss if cfg.experiment.rgb_loss == "mse" else F.l1_loss

@@ -5,7 +5,9 @@
 Same flags, optimisers (:117-122), per-iteration statements (:181-303, `joint_step`) and checkpoint keys (:347-357: `iter, nerf_optimizer,
 g_optim, d_optim, nerf_render, g, d, g_ema, latent_codes`), both load modes (:137-159).  Added flags: `--gan-ckpt` (the reference hard-codes
 pretrained_models/img_translation.ckpt, :144), `--percep {lpips,none}` (LPIPS needs the `lpips` package and its VGG weights; without them the
-harness refuses to start unless `none` is given, which drops the 0.1 * LPIPS term and says so), `--iters` / `--batch` for short runs.
+harness refuses to start unless `none` is given, which drops the 0.1 * LPIPS term and says so; `--percep native --percep-vgg PATH
+--percep-lin PATH` takes the term from this package's own module, model/lpips.py, with no `lpips` / torchvision import), `--iters` /
+`--batch` for short runs.
 What is different by design: scalars go to tensorboard only if it is installed (and to stdout every experiment.print_every iterations),
 there is no code tarball and no progress bar, the sample image is written through imgio, `latest.pt` is also written after the run's last
 iteration, and `--continue-training` continues the iteration count from the checkpoint's `iter` (the reference has that line commented out
@@ -272,7 +274,11 @@ def parse_args(argv=None):
     p.add_argument("--continue-training", action="store_true", default=False)
     p.add_argument("--gan-ckpt", type=str, default="pretrained_models/img_translation.ckpt",
                    help="pretrained image-translation GAN (g, d, g_ema) loaded next to a stage-one --ckpt")
-    p.add_argument("--percep", type=str, default="lpips", choices=["lpips", "none"], help="'none' drops the 0.1 * LPIPS term (no lpips package / weights)")
+    p.add_argument("--percep", type=str, default="lpips", choices=["lpips", "native", "none"],
+                   help="'native': this package's LPIPS-VGG module (model/lpips.py) on its own kernels; 'none' drops the 0.1 * LPIPS term "
+                        "(no lpips package / weights)")
+    p.add_argument("--percep-vgg", type=str, default="", help="--percep native: torchvision VGG16 weights (vgg16-*.pth)")
+    p.add_argument("--percep-lin", type=str, default="", help="--percep native: the lpips package's linear layers (weights/v0.1/vgg.pth)")
     p.add_argument("--iters", type=int, default=0, help="run iterations up to this one, exclusive (0 = styleUnet_args.iter)")
     p.add_argument("--batch", type=int, default=0, help="batch size (0 = styleUnet_args.batch)")
     return p.parse_args(argv)
@@ -296,6 +302,9 @@ def main(argv=None, device=None):
             raise RuntimeError("the 0.1 * LPIPS term of the stage-two loss needs the `lpips` package (VGG weights); install it or pass "
                                "--percep none") from e
         percep = lpips.LPIPS(net="vgg").to(device)
+    elif args.percep == "native":
+        from ..model.lpips import build_for_harness
+        percep = build_for_harness(args.percep_vgg, args.percep_lin, device)
     else:
         print("[train-hd] --percep none: the 0.1 * LPIPS(fake, gt) term of the reference loss is dropped")
     if deterministic_requested():

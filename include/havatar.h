@@ -457,6 +457,26 @@ int hav_s2_image_loss_bwd(float* gfake, float* grender, int64_t gsb, int64_t gsc
                           const float* mask, int64_t msb, int64_t msy, int64_t msx, const float* gt_lr, const float* fake,
                           const float* gt_hr, const float* gt_mask, int rgb_mse, int B, int r, int G, void* stream);
 
+/* The LPIPS-VGG perceptual loss of both training scripts (csrc/hav_lpips.hip; added within ABI 8: additive) -- the per-tap head and the
+ * ReLU gradient of the frozen VGG layers (train_avatar.py:24-29,138-142, train_avatarHD.py:268-274 of the reference call the `lpips` package).
+ *   head, one tap: f0, f1 [B,C,H,W] contiguous float32 feature maps, w [C] the tap's 1x1 weights,
+ *       a^ = f0 / (sqrt(sum_c f0^2) + 1e-10), b^ likewise;   out[b] = mean_{h,w} sum_c w[c] (a^ - b^)^2
+ *     fwd: two channel passes (norms, then the weighted squared difference of the normalised values); `partials` holds
+ *          hav_lpips_head_blocks(B, C, H, W) doubles (the workgroups' sums, added per sample in a fixed order by a second kernel).
+ *     bwd: gout [B] on the device; g0 / g1 [B,C,H,W] = d/df0, d/df1; either may be NULL (not wanted), not both.  With
+ *          r_k = 2 w_k (a^_k - b^_k) gout[b] / (H W), n = sqrt(sum f0^2):  d/df0_c = r_c / (n + eps) - f0_c (sum_k r_k f0_k) / (n (n + eps)^2),
+ *          for f1 the same with -r.  At n == 0 the second term is dropped (its limit): finite where autograd through sqrt gives NaN.
+ *   Any B, C, H, W >= 1; H W % 4 == 0 with 16-byte aligned maps takes 16-byte accesses, anything else 4-byte ones.  The same inputs give the
+ *   same bits on every launch (no float atomics).  NULL / sizes < 1: HAV_EINVAL; B > 65535 or oversize: HAV_EUNSUP; both before any launch.
+ *   relu mask: gc = g * [y > 0] over [B,C,HW]; gbias (may be NULL) [C] = sum_{b,p} gc, one workgroup per channel in float64.
+ * No allocation, no synchronisation: capturable. */
+int64_t hav_lpips_head_blocks(int B, int C, int H, int W);
+int hav_lpips_head_fwd(float* out, double* partials, const float* f0, const float* f1, const float* w, int B, int C, int H, int W,
+                       void* stream);
+int hav_lpips_head_bwd(float* g0, float* g1, const float* gout, const float* f0, const float* f1, const float* w, int B, int C, int H,
+                       int W, void* stream);
+int hav_relu_mask_bwd(float* gc, float* gbias, const float* g, const float* y, int B, int C, int64_t HW, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Trilinear x2 up-sampling of a [N,C,D,H,W] float32 volume and its adjoint -- nn.Upsample(scale_factor=2, mode='trilinear',
  * align_corners=False), the first stage of every UpConv3DBlock of the skinning-volume decoder
