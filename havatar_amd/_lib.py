@@ -123,7 +123,10 @@ def lib():
                        ("hav_lpips_head_blocks", [i32] * 4),
                        ("hav_lpips_head_fwd", [vp] * 5 + [i32] * 4 + [vp]),
                        ("hav_lpips_head_bwd", [vp] * 6 + [i32] * 4 + [vp]),
-                       ("hav_relu_mask_bwd", [vp] * 4 + [i32, i32, i64, vp])):
+                       ("hav_relu_mask_bwd", [vp] * 4 + [i32, i32, i64, vp]),
+                       ("hav_image_metrics_blocks", [i32] * 4),
+                       ("hav_image_metrics_f32", [vp] * 5 + [i32] * 4 + [f32, vp]),
+                       ("hav_image_metrics_u8", [vp] * 5 + [i32] * 3 + [vp])):
         try:
             fn = getattr(L, name)
         except AttributeError:

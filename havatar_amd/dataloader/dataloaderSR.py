@@ -11,11 +11,21 @@ from ._base import SplitFileDataset, make_render_cond_, worker_init_fn  # noqa: 
 class MultiView_ImgDataset(SplitFileDataset):
     skip_view = None                                 # every view is kept (dataloaderSR.py:44-49)
     device_rays = False                              # test mode: emit the 18-float camera record instead of the [N,11] ray table
+    with_gt = False                                  # test mode: also carry the photograph the frame can be scored against (--metrics)
+
+    def ground_truth(self, view):
+        """uint8 [H0,W0,3]: the photograph at its original resolution, white where the mask is off -- what 'train' mode builds below"""
+        img = np.array(imgio.imread_rgb(view["file_path"]))
+        if self.white_bg:
+            img[imgio.imread_rgb(view["mask_path"])[:, :, 0] <= 127] = 255
+        return torch.from_numpy(img)
 
     def load_data(self, frame_dict):
         view_idx, view, cam_K, pose = self.view_camera(frame_dict)
         if self.mode == "test" and self.device_rays and self.white_bg:
             data_dict = {"fidx": frame_dict["fidx"], "vidx": [int(view["view_name"])], "camera": self.camera_record(view, cam_K, pose)}
+            if self.with_gt:
+                data_dict["gt_img"] = self.ground_truth(view)
             return self.add_conditions(data_dict, frame_dict)
         select_inds = self.coords_yx
         mask = ray_m = None
@@ -27,6 +37,8 @@ class MultiView_ImgDataset(SplitFileDataset):
         mv_rays = self.rays_for(view_idx, view, cam_K, pose, select_inds, ray_m, with_mask=ray_m is not None)
         if self.mode == "test":
             data_dict = {"fidx": frame_dict["fidx"], "vidx": [int(view["view_name"])], "mv_rays": mv_rays}
+            if self.with_gt:
+                data_dict["gt_img"] = self.ground_truth(view)
         else:
             img = imgio.imread_rgb(view["file_path"])
             if self.white_bg:

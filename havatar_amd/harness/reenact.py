@@ -12,6 +12,7 @@ and the upsampler see a batch, the march takes B x R rays in one launch; files a
 differ from the same frames rendered alone by the encoders' rounding, 1e-4 on the render; a ragged last batch is rendered at its own size).
 """
 import argparse
+import json
 import os
 import time
 from concurrent.futures import ThreadPoolExecutor
@@ -48,6 +49,10 @@ def parse_args(argv=None):
     p.add_argument("--ckpt", type=str, default="", help="Path to load saved checkpoint from.")
     p.add_argument("--savedir", type=str, default="./renders/", help="Save images to this directory, if specified.")
     p.add_argument("--split", type=str, default=None, help="Split file (json) listing the frames to render.")
+    p.add_argument("--metrics", action="store_true", help="Score every frame against the split's photograph (PSNR, SSIM, LPIPS with both "
+                   "--percep paths) and write <savedir>/metrics.json.")
+    p.add_argument("--percep-vgg", type=str, default="", help="--metrics: torchvision VGG16 weights for LPIPS.")
+    p.add_argument("--percep-lin", type=str, default="", help="--metrics: lpips linear-layer weights for LPIPS.")
     return p.parse_args(argv)
 
 
@@ -97,11 +102,56 @@ def to_png_array(gen_img):
     return (gen_img[0].permute(1, 2, 0) * 255).clamp_(0, 255).to(torch.uint8).cpu().numpy()
 
 
+class FrameScores:
+    """--metrics: the scores of this rank's frames in a buffer on the frames' device, [n, 3] float64 = (ssim, mse, lpips).  add() enqueues work
+    on the current stream and reads nothing back; write() reads the buffer once, after the last frame."""
+
+    def __init__(self, n, device, percep):
+        self.buf = torch.zeros(max(n, 1), 3, dtype=torch.float64, device=device)
+        self.percep, self.rows = percep, []
+
+    def add(self, path, fidx, view, pred_u8, gt_u8):
+        """pred_u8, gt_u8 [H,W,3] uint8 on the buffer's device: the image as it is written, and the photograph"""
+        from .. import metrics
+        i = len(self.rows)
+        self.rows.append({"file": os.path.join("rgb", os.path.basename(path)), "fidx": fidx, "view": view})
+        self.buf[i, :2].copy_(metrics.ssim_mse(pred_u8[None], gt_u8[None])[0])
+        if self.percep is not None:
+            a, b = (t.permute(2, 0, 1)[None].float() / 127.5 - 1.0 for t in (pred_u8, gt_u8))
+            self.buf[i, 2].copy_(self.percep(a, b).reshape(()))
+
+    def write(self, savedir, rank, world):
+        from .. import metrics
+        vals = self.buf.cpu().numpy()
+        for row, v in zip(self.rows, vals):
+            row.update(ssim=float(v[0]), mse=float(v[1]), lpips=float(v[2]) if self.percep is not None else None)
+        note = "LPIPS-VGG on uint8 / 127.5 - 1" if self.percep is not None else "not evaluated: needs --percep-vgg and --percep-lin"
+        path = os.path.join(savedir, "metrics.json" if world == 1 else "metrics_rank%dof%d.json" % (rank, world))
+        with open(path, "w") as f:
+            json.dump(metrics.table(self.rows, lpips_note=note), f, indent=1)
+        return path
+
+
+def check_metric_sizes(cfg, split):
+    """--metrics compares the written image with the photograph pixel by pixel: refuse before anything is rendered when the two differ in size"""
+    with open(split) as f:
+        img_res = json.load(f)["img_res"]
+    out_size = cfg.models.StyleUnet.out_size
+    if out_size != img_res:
+        raise RuntimeError("--metrics: StyleUnet.out_size %d differs from the split's img_res %d: the frames cannot be scored against its "
+                           "photographs" % (out_size, img_res))
+
+
 def main(argv=None, device=None, style=None):
     args = parse_args(argv)
     os.makedirs(os.path.join(args.savedir, "rgb"), exist_ok=True)
     with open(args.config, "r") as f:
         cfg = CfgNode(yaml.load(f, Loader=yaml.FullLoader))
+    if args.metrics:
+        check_metric_sizes(cfg, args.split)
+        if bool(args.percep_vgg) != bool(args.percep_lin):
+            raise RuntimeError("--metrics: LPIPS needs both --percep-vgg PATH (torchvision VGG16 weights) and --percep-lin PATH (lpips linear "
+                               "layers); pass both, or neither for PSNR and SSIM only")
     seed = cfg.experiment.randomseed
     np.random.seed(seed)
     torch.manual_seed(seed)
@@ -124,6 +174,16 @@ def main(argv=None, device=None, style=None):
     # HIP: the loader ships 18 camera floats per frame and the ray table is built on the device
     val_loader.dataset.device_rays = device.type == "cuda" and os.environ.get("HAVATAR_DEVICE_RAYS", "1") != "0"
     ray_cache = {}
+    scores = None
+    if args.metrics:
+        val_loader.dataset.with_gt = True
+        percep = None
+        if args.percep_vgg and args.percep_lin:
+            from ..model.lpips import build_for_harness
+            percep = build_for_harness(args.percep_vgg, args.percep_lin, device)
+        else:
+            print("[metrics] no --percep-vgg / --percep-lin: LPIPS is omitted, PSNR and SSIM only")
+        scores = FrameScores(len(mine), device, percep)
     # this rank's frames only, read ahead by worker processes (the reference reads every frame in the main process)
     fbatch = max(1, int(os.environ.get("HAVATAR_FRAME_BATCH", "1")))
     frames = torch.utils.data.DataLoader(torch.utils.data.Subset(val_loader.dataset, mine), batch_size=fbatch, shuffle=False,
@@ -142,6 +202,7 @@ def main(argv=None, device=None, style=None):
             n = int(val_batch["fidx"].shape[0])
             inp = frame_inputs(idx, val_batch, device, size=val_loader.dataset.img_h, cache=ray_cache)
             styles = [style if n == 1 else style.expand(n, -1)]
+            gt_imgs = val_batch["gt_img"].to(device, non_blocking=True) if scores is not None else None
             if use_graph:
                 tens = {k_: v for k_, v in inp.items() if torch.is_tensor(v) and k_ != "fidx"}
                 if n not in graphed:
@@ -161,7 +222,10 @@ def main(argv=None, device=None, style=None):
                 path = os.path.join(args.savedir, "rgb", f"{name}_{k:02d}.png")
                 written.append(path)
                 if device.type != "cuda":
-                    pending.append(writers.submit(imgio.imwrite_rgb, path, to_png_array(gen_img)))
+                    arr = to_png_array(gen_img)
+                    if scores is not None:
+                        scores.add(path, int(name), k, torch.from_numpy(arr), gt_imgs[b])
+                    pending.append(writers.submit(imgio.imwrite_rgb, path, arr))
                     continue
                 # two-slot read-back ring: frame n's uint8 image is copied to pinned memory asynchronously and handed to the PNG
                 # threads while frame n+1 is being prepared and launched, so the GPU does not idle during host work
@@ -176,6 +240,8 @@ def main(argv=None, device=None, style=None):
                 dev_u8.copy_((gen_img[0].permute(1, 2, 0) * 255).clamp_(0, 255))          # float -> uint8 truncation, as to_png_array
                 host_u8.copy_(dev_u8, non_blocking=True)
                 ev.record()
+                if scores is not None:                                                     # on the device, after the read-back was enqueued
+                    scores.add(path, int(name), k, dev_u8, gt_imgs[b])
                 if in_flight is not None:                                                  # finish the PREVIOUS frame now
                     p_path, p_slot = in_flight
                     ring[p_slot][2].synchronize()
@@ -193,6 +259,8 @@ def main(argv=None, device=None, style=None):
         print("[rank %d] %d frames; first frame %.2f s (solver search + graph capture), then %.1f ms per frame end to end "
               "(read, render %dx%d, upsample %dx%d, PNG)" % (rank, len(written), t_loop - t_first, 1e3 * dt / (len(written) - 1),
                                                             nerf_render.render_size, nerf_render.render_size, gen_img.shape[-1], gen_img.shape[-2]))
+    if scores is not None:
+        print("[metrics] %s" % scores.write(args.savedir, rank, world))
     print("Done!")
     return written
 

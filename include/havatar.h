@@ -477,6 +477,24 @@ int hav_lpips_head_bwd(float* g0, float* g1, const float* gout, const float* f0,
                        int W, void* stream);
 int hav_relu_mask_bwd(float* gc, float* gbias, const float* g, const float* y, int B, int C, int64_t HW, void* stream);
 
+/* Image-quality metrics of an image pair (csrc/hav_metrics.hip; added within ABI 8: additive) -- mean SSIM and the mean squared error behind
+ * PSNR in one pass over the two images.  No reference counterpart: the reference leaves evaluation to outside packages.
+ *   SSIM (Wang et al. 2004) per channel: 11-tap Gaussian window, sigma 1.5, normalised to sum 1, separable, VALID windows only (the map is
+ *   [H-10, W-10]); C1 = (0.01 L)^2, C2 = (0.03 L)^2; ssim = ((2 mx my + C1)(2 sxy + C2)) / ((mx^2 + my^2 + C1)(sxx + syy + C2)); the value is
+ *   the mean over the map and the channels, per sample.  The five moments are accumulated in float64 (no cancellation on flat images).
+ *   f32: a, b [B,C,H,W] contiguous float32, L = data_range.   u8: a, b [B,H,W,3] channels-last uint8, taken as 0..255 with L = 255.
+ *   out [B,2] float32 = { mean SSIM, mean squared error over all C H W elements } -- f32: in input units^2; u8: in [0,1]^2 units (/ 255^2), from an
+ *   exact integer sum.  map: NULL, or [B,C,H-10,W-10] float32 (u8: C = 3, planar) that receives the SSIM map.
+ *   partials: hav_image_metrics_blocks(B, C, H, W) doubles (u8: C = 3) -- two per workgroup of 32 x 32 map elements, added per sample in a
+ *   fixed order by a second kernel; 0 for sizes the entries refuse.
+ * The same inputs give the same bits on every launch (no atomics).  NULL out / partials / a / b, sizes < 1, data_range not positive and
+ * finite: HAV_EINVAL; H < 11, W < 11 or more than 2^31 - 1 workgroups: HAV_EUNSUP; both before any launch.  W % 4 == 0 with 16-byte aligned
+ * float images takes 16-byte loads, anything else 4-byte (u8: 1-byte) ones.  No allocation, no synchronisation: capturable. */
+int64_t hav_image_metrics_blocks(int B, int C, int H, int W);
+int hav_image_metrics_f32(float* out, double* partials, float* map, const float* a, const float* b, int B, int C, int H, int W,
+                          float data_range, void* stream);
+int hav_image_metrics_u8(float* out, double* partials, float* map, const uint8_t* a, const uint8_t* b, int B, int H, int W, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Trilinear x2 up-sampling of a [N,C,D,H,W] float32 volume and its adjoint -- nn.Upsample(scale_factor=2, mode='trilinear',
  * align_corners=False), the first stage of every UpConv3DBlock of the skinning-volume decoder
