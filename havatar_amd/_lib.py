@@ -5,6 +5,8 @@ Fails loudly: there is no CPU or PyTorch fallback behind these entry points.
 import ctypes as C
 import os
 
+from . import switches
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libhavatar_hip.so")
 
@@ -57,7 +59,7 @@ def lib():
     global _lib
     if _lib is not None:
         return _lib
-    path = os.environ.get("HAVATAR_LIB", LIB_PATH)      # kernel experiments: an alternative build of the SAME library
+    path = switches.path("HAVATAR_LIB", LIB_PATH)      # kernel experiments: an alternative build of the SAME library
     if not os.path.exists(path):
         raise HavatarLibraryError(
             f"{path} is missing: build it with `python -m havatar_amd.build` "

@@ -7,6 +7,8 @@ import os
 import subprocess
 import sys
 
+from . import switches
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
@@ -38,7 +40,7 @@ def check_compiler(hipcc):
     if not tested:
         msg = ("hipcc differs from the compiler this library's kernels were validated with:\n  found  %s\n  tested %s\n"
                "Re-run tools/stress_production.py and the -m gpu determinism tests on a GPU with the new build." % (ver, TESTED_HIPCC))
-        if os.environ.get("HAVATAR_REQUIRE_TESTED_HIPCC", "0") == "1":
+        if switches.off("HAVATAR_REQUIRE_TESTED_HIPCC"):
             raise RuntimeError(msg)
         import warnings
         warnings.warn(msg, RuntimeWarning, stacklevel=2)

@@ -9,6 +9,8 @@ import os
 
 import torch
 
+from . import switches
+
 _WEIGHTS_EPOCH = [0]
 _WARNED = [False]
 
@@ -87,7 +89,7 @@ class GraphedTrainStep:
         self.static = {k: v.clone() for k, v in example.items()}
         self.optimizer = optimizer
         optimizer.zero_grad(set_to_none=True)
-        shape = os.environ.get("HAVATAR_GRAPH_SHAPE") == "1"          # development aid: print the captured graph's topology (tools/graph_shape.py)
+        shape = switches.off("HAVATAR_GRAPH_SHAPE")          # development aid: print the captured graph's topology (tools/graph_shape.py)
         self.graph = torch.cuda.CUDAGraph(keep_graph=True) if shape else torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph, stream=stream, capture_error_mode="thread_local"):
             self.loss, self.aux = step_fn(**self.static)

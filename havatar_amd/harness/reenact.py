@@ -22,6 +22,7 @@ import torch
 import yaml
 
 from . import per_rank_miopen_cache
+from .. import switches
 from ..dataloader import imgio
 from ..dataloader.dataloaderSR import Loader
 from ..frames import shard_frames
@@ -172,7 +173,7 @@ def main(argv=None, device=None, style=None):
     val_loader = Loader(split_file=args.split, mode="test", batch_size=1, options=cfg, down_sample=cfg.dataset.down_sample)
     mine = list(shard_frames(len(val_loader.dataset), rank, world))
     # HIP: the loader ships 18 camera floats per frame and the ray table is built on the device
-    val_loader.dataset.device_rays = device.type == "cuda" and os.environ.get("HAVATAR_DEVICE_RAYS", "1") != "0"
+    val_loader.dataset.device_rays = device.type == "cuda" and switches.on("HAVATAR_DEVICE_RAYS")
     ray_cache = {}
     scores = None
     if args.metrics:
@@ -185,12 +186,12 @@ def main(argv=None, device=None, style=None):
             print("[metrics] no --percep-vgg / --percep-lin: LPIPS is omitted, PSNR and SSIM only")
         scores = FrameScores(len(mine), device, percep)
     # this rank's frames only, read ahead by worker processes (the reference reads every frame in the main process)
-    fbatch = max(1, int(os.environ.get("HAVATAR_FRAME_BATCH", "1")))
+    fbatch = max(1, switches.integer("HAVATAR_FRAME_BATCH"))
     frames = torch.utils.data.DataLoader(torch.utils.data.Subset(val_loader.dataset, mine), batch_size=fbatch, shuffle=False,
-                                         num_workers=int(os.environ.get("HAVATAR_WORKERS", 4)), pin_memory=device.type == "cuda")
-    use_graph = device.type == "cuda" and os.environ.get("HAVATAR_GRAPH", "1") != "0"
+                                         num_workers=switches.integer("HAVATAR_WORKERS", 4), pin_memory=device.type == "cuda")
+    use_graph = device.type == "cuda" and switches.on("HAVATAR_GRAPH")
     graphed, graphed2, written = {}, {}, []            # hipGraphs per batch size (the last batch of a split may be ragged)
-    writers = ThreadPoolExecutor(max_workers=int(os.environ.get("HAVATAR_PNG_THREADS", 12)))    # PNG deflate off the critical path (a 1024^2 frame is ~70 ms of zlib on one core)
+    writers = ThreadPoolExecutor(max_workers=switches.integer("HAVATAR_PNG_THREADS"))    # PNG deflate off the critical path (a 1024^2 frame is ~70 ms of zlib on one core)
     pending, ring, in_flight = [], [None, None], None
     t_first = t_loop = None
     with torch.no_grad():

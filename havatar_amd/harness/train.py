@@ -22,7 +22,9 @@ import yaml
 
 from ..dataloader import imgio
 from ..dataloader.dataloader import Loader
+from .. import switches
 from ..model.nerf_trainer import Trainer
+from ..native import train_ops
 from ..utils.cfgnode import CfgNode
 from ..utils.training_util import mse2psnr
 
@@ -88,8 +90,8 @@ def training_loss(trainer, cfg, inp, target, ray_mask, rgb_loss_func, percep_los
 
 def graph_training_enabled(device, percep_loss_fn=None):
     """The step runs as one hipGraph launch (graph.GraphedTrainStep) on HIP devices unless HAVATAR_TRAIN_GRAPH=0."""
-    return (torch.device(device).type == "cuda" and percep_loss_fn is None and os.environ.get("HAVATAR_TRAIN_GRAPH", "1") != "0"
-            and os.environ.get("HAVATAR_HIP_TRAIN", "1") != "0")       # the ATen statement of the march reads host tensors
+    return (torch.device(device).type == "cuda" and percep_loss_fn is None and switches.on("HAVATAR_TRAIN_GRAPH")
+            and switches.on("HAVATAR_HIP_TRAIN"))       # the ATen statement of the march reads host tensors
 
 
 def make_optimizer(cfg, trainer, graph):
@@ -97,7 +99,7 @@ def make_optimizer(cfg, trainer, graph):
     if graph and cfg.optimizer.type in ("Adam", "AdamW", "NAdam", "RAdam", "Adamax", "Adagrad", "RMSprop", "SGD", "ASGD", "Adadelta", "Rprop"):
         # capturable: the step counter and the learning rate live on the device, so the optimiser update can be replayed
         kw = {"capturable": True} if cfg.optimizer.type != "SGD" else {}
-        if cfg.optimizer.type in ("Adam", "AdamW") and os.environ.get("HAVATAR_FUSED_ADAM", "1") != "0":
+        if cfg.optimizer.type in ("Adam", "AdamW") and switches.on("HAVATAR_FUSED_ADAM"):
             kw["fused"] = True            # one multi-tensor kernel per parameter bucket instead of ~8 foreach passes (same update formula)
     return getattr(torch.optim, cfg.optimizer.type)([{"params": list(trainer.parameters())}], lr=cfg.optimizer.lr, **kw)
 
@@ -126,14 +128,14 @@ def enable_determinism(on=True):
     scatter sums in 64-bit fixed point (native/train_ops.py::deterministic: the float atomics of the default route land in a different
     order every time), MIOpen is restricted to deterministic solvers (torch.backends.cudnn.deterministic: the default solver of the 16^2
     convolutions is what makes even the FORWARD differ between runs), ATen's index / scatter adds take their deterministic forms."""
-    if os.environ.get("HAVATAR_DET_MIOPEN", "1") != "0":          # (A/B: the parts one by one)
+    if switches.on("HAVATAR_DET_MIOPEN"):          # (A/B: the parts one by one)
         torch.backends.cudnn.deterministic = bool(on)
-    if os.environ.get("HAVATAR_DET_ATEN", "1") != "0":
+    if switches.on("HAVATAR_DET_ATEN"):
         torch.use_deterministic_algorithms(bool(on), warn_only=True)
 
 
 def deterministic_requested():
-    return os.environ.get("HAVATAR_DETERMINISTIC", "0") == "1"
+    return train_ops.deterministic()
 
 
 class StepRunner:
@@ -180,7 +182,7 @@ class StepRunner:
                 self.side.wait_stream(torch.cuda.current_stream(dev))
                 self.graphed = GraphedTrainStep(lambda target, ray_mask, **kw: self._loss(target, ray_mask, **kw), self.optimizer,
                                                 dict(tens, target=target, ray_mask=ray_mask),
-                                                stream=None if os.environ.get("HAVATAR_GRAPH_CAPTURE_STREAM") == "own" else self.side)          # ("own": the old, forking capture; A/B only)
+                                                stream=None if switches.choice("HAVATAR_GRAPH_CAPTURE_STREAM") == "own" else self.side)          # ("own": the old, forking capture; A/B only)
                 torch.cuda.current_stream(dev).wait_stream(self.side)
             loss, aux = self.graphed(**tens, target=target, ray_mask=ray_mask)
             parts = {k: v for k, v in aux.items() if k != "_mse"}
@@ -285,7 +287,7 @@ def main(argv=None, device=None):
         print("[train] --percep none: the 0.05 * LPIPS(patch) term of the reference loss is dropped")
     rgb_loss_func = F.mse_loss if cfg.experiment.rgb_loss == "mse" else F.l1_loss
     split = os.path.join(args.datadir, "sv_v31_all.json")
-    workers = int(os.environ.get("HAVATAR_WORKERS", 8))
+    workers = switches.integer("HAVATAR_WORKERS", 8)
     train_loader = Loader(split_file=split, mode="train", batch_size=2, num_workers=workers, down_sample=cfg.dataset.down_sample,
                           options=cfg, white_bg=True)
     val_loader = Loader(split_file=split, shuffle=True, mode="val", batch_size=1, num_workers=min(workers, 1), down_sample=1.0,
@@ -310,7 +312,7 @@ def main(argv=None, device=None):
         optimizer.load_state_dict(checkpoint["optimizer_state_dict"])
         start_iter = checkpoint["iter"]
     elif trainer.headpose_skin_net is not None:
-        trainer.headpose_skin_net.pretrain_wc(num_iter=int(os.environ.get("HAVATAR_PRETRAIN_WC", 3000)), vol_thr=cfg.models.coarse.Head_bounding)
+        trainer.headpose_skin_net.pretrain_wc(num_iter=switches.integer("HAVATAR_PRETRAIN_WC"), vol_thr=cfg.models.coarse.Head_bounding)
     i, steps_done = start_iter, 0
     loss, psnr = None, None
     run_step = StepRunner(trainer, cfg, optimizer, rgb_loss_func, percep_loss_fn, graph=use_graph)
@@ -321,7 +323,7 @@ def main(argv=None, device=None):
             i += 1
             inp, target, ray_mask = step_inputs(idx, batch, device)
             loss, parts, psnr = run_step(inp, target, ray_mask)
-            if os.environ.get("HAVATAR_NAN_TRACE"):
+            if switches.choice("HAVATAR_NAN_TRACE"):
                 from ..native import conv as _nconv
                 bad = [(k, n) for k, (n, f) in enumerate(_nconv._NAN_TRACE or []) if not bool(f)]
                 if bad:

@@ -23,6 +23,7 @@ import torch
 import torch.nn.functional as F
 import yaml
 
+from .. import switches
 from ..dataloader import imgio
 from ..dataloader.dataloaderSR import Loader
 from ..model.nerf_trainer import Trainer
@@ -309,7 +310,7 @@ def main(argv=None, device=None):
         print("[train-hd] --percep none: the 0.1 * LPIPS(fake, gt) term of the reference loss is dropped")
     if deterministic_requested():
         enable_determinism()
-    workers = int(os.environ.get("HAVATAR_WORKERS", 8))
+    workers = switches.integer("HAVATAR_WORKERS", 8)
     train_loader = Loader(split_file=os.path.join(args.datadir, "sv_v31_all.json"), down_sample=cfg.dataset.down_sample, mode="train",
                           batch_size=su_args.batch, num_workers=workers, options=cfg, white_bg=True)
     nets = build_nets(cfg, su_args, len(train_loader.dataset), device)

@@ -3,13 +3,13 @@
 here; gather + PE + MLP are inside the fused ray-march kernel.  `sample_pts_triplane_feat` / `forward` keep the PyTorch
 statement for CPU tensors and autograd.  Only enc_mode='split' (the Trainer's choice) is implemented."""
 import logging
-import os
 
 import torch
 import torch.nn as nn
 
 from .network.embedder import get_embedder
 from .styleUnet import StyleGAN_zxc
+from .. import switches
 from ..utils.sh_util import eval_sh
 from ..utils.util import create_UniformBoxWarp, sample_from_triplane_new
 
@@ -95,7 +95,7 @@ class ConditionalTriplaneNeRFModel_multiRender_split_view(nn.Module):
         if left.shape[1] > 3:
             left = left[:, :-1]
         yz_in = torch.cat([left, right], dim=1)
-        if front.is_cuda and not torch.is_grad_enabled() and os.environ.get("HAVATAR_ENC_STREAMS", "1") != "0":
+        if front.is_cuda and not torch.is_grad_enabled() and switches.on("HAVATAR_ENC_STREAMS"):
             # The two generators are independent until the stack, and at 16^2..64^2 most of their ~90 launches each leave the
             # GPU nearly idle: run them on two HIP streams (fork/join by events; captured as two branches of the frame's hipGraph).
             cur = torch.cuda.current_stream(front.device)
@@ -118,7 +118,7 @@ class ConditionalTriplaneNeRFModel_multiRender_split_view(nn.Module):
         q = self.gridwarper(batch_pts)
         planes = self.triPlane_embeddings if bidx is None else self.triPlane_embeddings[:, bidx]
         if q.is_cuda and q.dtype == torch.float32 and q.ndim == 3 and planes.ndim == 5 and planes.shape[0] == 2 \
-                and os.environ.get("HAVATAR_HIP_GATHER", "1") != "0":
+                and switches.on("HAVATAR_HIP_GATHER"):
             # training on HIP tensors: one coalesced gather / scatter kernel pair instead of ATen's grid_sampler on NCHW planes
             from ..native.gather import triplane_gather
             return triplane_gather(q, planes)
@@ -137,7 +137,7 @@ class ConditionalTriplaneNeRFModel_multiRender_split_view(nn.Module):
         matrix cores, activations recomputed in the backward (native/mlp_train.py).  HAVATAR_TRAIN_MLP=torch keeps the fp32
         nn.Linear statement (rocBLAS), which is what CPU tensors always take."""
         if (x.is_cuda and x.dtype == torch.float32 and x.ndim == 2 and x.shape[1] == 176 and self.sh_deg == 0 and x.shape[0] >= 1024
-                and torch.is_grad_enabled() and os.environ.get("HAVATAR_TRAIN_MLP", "bf16") == "bf16"):
+                and torch.is_grad_enabled() and switches.choice("HAVATAR_TRAIN_MLP") == "bf16"):
             from ..native import mlp_train
             ws = self.mlp_tensors()
             if [tuple(w.shape) for w in ws] == mlp_train._SHAPES:          # other widths (rgb_feat_dim != 3, ...) keep the ATen statement

@@ -5,13 +5,12 @@ Difference: `predict_and_render_radiance` on HIP tensors without autograd is ONE
 rays it is given (ray sampling, skinning lookup, tri-plane gather, PE, MLP, compositing, resampling, second pass), and
 `nerf_forward` therefore does not chunk (the reference's chunksize loop only bounds activation memory, :66-71).  CPU
 tensors and autograd-tracked calls take the PyTorch statement of the same algorithm (the reference runs there too)."""
-import os
-
 import numpy as np
 import torch
 from einops import rearrange
 
 from . import nerf_model
+from .. import switches
 from .Skinning_Field import Deformation_Field_new
 from ..render import RayMarcher
 from ..utils.nerf_util import sample_pdf, volume_render_radiance_field
@@ -98,7 +97,7 @@ class Trainer(torch.nn.Module):
             # not be one piece on any device): at most HAVATAR_TRAIN_CHUNK_RAYS rays per chunk over the batch (default 32768 = eight cfg5
             # steps' worth, ~2.6 GB of field inputs), never less than the reference's chunk
             if rays.is_cuda:
-                cap = max(int(os.environ.get("HAVATAR_TRAIN_CHUNK_RAYS", "32768")), opt.chunksize)
+                cap = max(switches.integer("HAVATAR_TRAIN_CHUNK_RAYS"), opt.chunksize)
                 chunk = min(rays.shape[1], max(cap // rays.shape[0], 1))
             else:
                 chunk = opt.chunksize // rays.shape[0]
@@ -199,9 +198,10 @@ class Trainer(torch.nn.Module):
         # Samples per pass: hav_composite_* holds 64 (a lane per sample), hav_composite_long_* 128 (two per lane); the latter is opt-in
         # (HAVATAR_COMPOSITE_LONG=1, read here).  Without it a wider sampling takes the ATen statement below, and says so once.
         widest = max(opt.num_coarse, opt.num_coarse // 2 + opt.num_coarse % 2 + opt.num_fine)
-        fused = (ro.is_cuda and ro.dtype == torch.float32 and self.model_coarse.sh_deg == 0 and os.environ.get("HAVATAR_HIP_TRAIN", "1") != "0")
+        fused = (ro.is_cuda and ro.dtype == torch.float32 and self.model_coarse.sh_deg == 0 and switches.on("HAVATAR_HIP_TRAIN"))
         if fused and widest > 64:
-            long_on = os.environ.get("HAVATAR_COMPOSITE_LONG", "0") == "1"
+            from ..native.train_ops import composite_long_enabled
+            long_on = composite_long_enabled()
             if not long_on and 64 < widest <= 128:
                 _warn_wide_sampling(widest)
             fused = long_on and widest <= 128
@@ -218,12 +218,12 @@ class Trainer(torch.nn.Module):
             pts = (ro[..., None, :] + rd[..., None, :] * zv[..., :, None]).reshape(B, -1, 3)
             mc = self.model_coarse
             ws = mc.mlp_tensors() if (torch.is_grad_enabled() and pts.shape[0] * pts.shape[1] >= 1024 and mc.sh_deg == 0
-                                      and os.environ.get("HAVATAR_TRAIN_MLP", "bf16") == "bf16" and os.environ.get("HAVATAR_FIELD_MLP", "1") != "0") else None
+                                      and switches.choice("HAVATAR_TRAIN_MLP") == "bf16" and switches.on("HAVATAR_FIELD_MLP")) else None
             # patch training (dataloader.py:93-121: a 64 x 64 patch, row-major): neighbouring rays are neighbouring pixels.  With
             # HAVATAR_FIELD_ROWS=1 the scatter of the field-input gradients merges across 16 rays instead of along one (same sums;
             # native/train_ops.py::_field_backward).  Off by default: faster on dense in-box patches (1.82 -> 1.59 ms per call,
             # tools/bench_field_rows.py), slower inside this step on the harness' frames (0.685 -> 0.754 ms, profiles/r05_field_rows_ab.txt)
-            rows = zv.shape[-1] if (os.environ.get("HAVATAR_FIELD_ROWS", "0") == "1" and bool(getattr(self.cfg.experiment, "patch_rgb", False))
+            rows = zv.shape[-1] if (switches.off("HAVATAR_FIELD_ROWS") and bool(getattr(self.cfg.experiment, "patch_rgb", False))
                                     and R % 16 == 0) else 0
             if ws is not None and field_mlp_eligible(planes, ws):
                 # field inputs + bf16-MFMA radiance MLP as one autograd node with bf16 rows in between (native/train_ops.py::FieldMlp)
@@ -256,7 +256,7 @@ class Trainer(torch.nn.Module):
         if opt.num_fine <= 0:
             return rs(rgb_c), rs(depth_c), rs(acc_c), rs(weights.max(dim=-1)[0]), None, None, None
         zf = z.reshape(-1, z.shape[-1])
-        if fused and 3 <= zf.shape[-1] <= 128 and os.environ.get("HAVATAR_RESAMPLE", "hip") != "aten":
+        if fused and 3 <= zf.shape[-1] <= 128 and switches.choice("HAVATAR_RESAMPLE") != "aten":
             # the three statements + sample_pdf as one launch (hav_resample_depths; ~30 ATen launches otherwise).  The stratified
             # draw is made here exactly where sample_pdf makes it (utils/nerf_util.py:95: on the CPU generator; on the device
             # generator while a training step is being captured, like utils/nerf_util.py::sample_pdf of this package)

@@ -6,10 +6,11 @@ route and also takes InstanceNorm3d + ReLU (train_ops.inorm_relu3d) and final_co
 csrc/hav_decoder.hip; without it both stay the ATen statements.
 state_dict keys: init_lc, filters.{i}.up.1.{weight,bias}, final_conv.{weight,bias}."""
 import math
-import os
 
 import torch
 import torch.nn as nn
+
+from ... import switches
 
 
 class Upsample2xTrilinear(nn.Module):
@@ -57,7 +58,7 @@ class UpConv3DBlock(nn.Module):
             if conv3d_small_eligible(y, self.up[1]):
                 # volumes of <= 8^3 voxels: the convolution as GEMMs over an explicit patch matrix (native/train_ops.py::Conv3dSmall)
                 return conv3d_small(y, self.up[1])
-            if conv3d_k3_eligible(y, self.up[1]) and (native or os.environ.get("HAVATAR_CONV3D") == "hip"):
+            if conv3d_k3_eligible(y, self.up[1]) and (native or switches.choice("HAVATAR_CONV3D") == "hip"):
                 # opt-in: the 16^3 - 64^3 layers on the native 3x3x3 kernels (native/train_ops.py::Conv3dK3); MIOpen stays the default
                 from ...native import train_ops
                 return train_ops.conv3d_k3(y, self.up[1])
@@ -71,7 +72,7 @@ class UpConv3DBlock(nn.Module):
         """relu(forward(x)), what VolumeDecoder applies to every block.  With HAVATAR_DECODER=hip the normalisation and the ReLU are one
         node of this library (native/train_ops.py::InormRelu3d) and the 16^3 - 64^3 convolutions take conv3d_k3; whatever is not
         eligible keeps today's statements."""
-        if os.environ.get("HAVATAR_DECODER") == "hip" and x.is_cuda:
+        if switches.choice("HAVATAR_DECODER") == "hip" and x.is_cuda:
             from ...native import train_ops
             y = self._conv(x, True)
             if train_ops.inorm_relu3d_eligible(y, self.norm):
@@ -98,7 +99,7 @@ class VolumeDecoder(nn.Module):
         x = self.init_lc
         for f in self.filters:
             x = f.forward_relu(x)
-        if os.environ.get("HAVATAR_DECODER") == "hip" and x.is_cuda:
+        if switches.choice("HAVATAR_DECODER") == "hip" and x.is_cuda:
             from ...native import train_ops
             if train_ops.final_conv_sigmoid_eligible(x, self.final_conv):
                 return train_ops.final_conv_sigmoid(x, self.final_conv)

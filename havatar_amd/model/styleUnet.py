@@ -16,16 +16,24 @@ import torch
 from torch import nn
 from torch.nn import functional as F
 
-import os
-
 from .op import FusedLeakyReLU, conv2d_gradfix, fused_leaky_relu, upfirdn2d
+from .. import switches
 from ..graph import weights_epoch
 from ..native import conv as _conv
 
 
 def _fused_conv_enabled():
     """HAVATAR_FUSED_CONV=0 keeps every convolution on MIOpen (A/B runs)."""
-    return os.environ.get("HAVATAR_FUSED_CONV", "1") != "0"
+    return switches.on("HAVATAR_FUSED_CONV")
+
+
+def _hip_train():
+    return switches.on("HAVATAR_HIP_TRAIN")
+
+
+def _conv_s2():
+    return switches.on("HAVATAR_CONV_S2")
+
 
 _CHANNELS = lambda cm: {4: 512, 8: 512, 16: 512, 32: 512, 64: 256 * cm, 128: 128 * cm, 256: 64 * cm, 512: 32 * cm, 1024: 16 * cm}
 
@@ -129,8 +137,8 @@ class EqualLinear(nn.Module, _InferenceCache):
         self.lr_mul = lr_mul
 
     def forward(self, input):
-        if (not self.activation and input.is_cuda and torch.is_grad_enabled() and os.environ.get("HAVATAR_HIP_TRAIN", "1") != "0"
-                and os.environ.get("HAVATAR_EQUAL_LINEAR", "1") != "0"):
+        if (not self.activation and input.is_cuda and torch.is_grad_enabled() and _hip_train()
+                and switches.on("HAVATAR_EQUAL_LINEAR")):
             from ..native.train_ops import equal_linear, equal_linear_eligible
             if equal_linear_eligible(input, self.weight, self.bias):
                 # training: the scalar products over the parameters, the GEMM and their adjoints as one launch each way (hav_equal_linear_*)
@@ -179,7 +187,7 @@ class ModulatedConv2d(nn.Module, _InferenceCache):
 
     def fused_upconv_ok(self, input):
         """the up-sampling 3x3 (conv_transpose2d stride 2 -> 4x4 blur with padding (1,1)) in a shape hav_gemm_split + hav_upconv_finish take."""
-        return (self.kernel_size == 3 and self.upsample and _fused_conv_enabled() and os.environ.get("HAVATAR_FUSED_UPCONV", "1") != "0"
+        return (self.kernel_size == 3 and self.upsample and _fused_conv_enabled() and switches.on("HAVATAR_FUSED_UPCONV")
                 and tuple(self.blur.kernel.shape) == (4, 4) and tuple(self.blur.pad) == (1, 1) and _conv.upconv_eligible(input, self.weight[0]))
 
     def packed_upconv(self):
@@ -203,7 +211,7 @@ class ModulatedConv2d(nn.Module, _InferenceCache):
         s = mod(style)
         if not self.demodulate:
             return s, None
-        if s.is_cuda and s.dtype == torch.float32 and torch.is_grad_enabled() and os.environ.get("HAVATAR_HIP_TRAIN", "1") != "0":
+        if s.is_cuda and s.dtype == torch.float32 and torch.is_grad_enabled() and _hip_train():
             from ..native.train_ops import demod            # training on HIP tensors: one autograd node (hav_demod_fwd / _bwd)
             return s, demod(s, self.weight[0], self.scale, self.eps)
         return s, torch.rsqrt(torch.matmul(s * s, wsq_fn()) + self.eps)
@@ -273,8 +281,8 @@ class ConvLayer(nn.Sequential):
     def forward(self, input):
         ec = self[0]
         if (len(self) > 1 and isinstance(self[0], Blur) and isinstance(self[1], EqualConv2d) and input.is_cuda and input.dtype == torch.float32
-                and not torch.is_grad_enabled() and _fused_conv_enabled() and os.environ.get("HAVATAR_CONV_S2", "1") != "0"
-                and os.environ.get("HAVATAR_S2_INFER", "1") != "0"):
+                and not torch.is_grad_enabled() and _fused_conv_enabled() and _conv_s2()
+                and switches.on("HAVATAR_S2_INFER")):
             # HIP inference, down-sampling layer: Blur (hav_upfirdn2d) -> EqualConv2d stride 2 + bias + leaky-ReLU as one kernel
             # (hav_conv3x3s2_split) instead of MIOpen's Im2d2Col + fp32 GEMM + the activation launch: 78.6 against 110.8 us on the
             # encoders' 256 -> 512 layer, 49.5 against 69.1 us on the 512 -> 512 one, blur included (tools/bench_s2.py,
@@ -290,8 +298,8 @@ class ConvLayer(nn.Sequential):
             out = ec(xb)
             return self[2](out) if len(self) > 2 else out
         if (len(self) > 1 and isinstance(self[0], Blur) and isinstance(self[1], EqualConv2d) and input.is_cuda and input.dtype == torch.float32
-                and torch.is_grad_enabled() and _fused_conv_enabled() and os.environ.get("HAVATAR_CONV_S2", "1") != "0"
-                and os.environ.get("HAVATAR_HIP_TRAIN", "1") != "0" and os.environ.get("HAVATAR_S2_TRAIN", "1") != "0"):
+                and torch.is_grad_enabled() and _fused_conv_enabled() and _conv_s2()
+                and _hip_train() and switches.on("HAVATAR_S2_TRAIN")):
             # HIP training, down-sampling layer: the Blur (its own autograd op) -> EqualConv2d stride 2 + bias + leaky-ReLU as one autograd
             # node whose forward is hav_conv3x3s2_split (native/conv.py::_S2ConvBlock)
             ec, bl = self[1], self[0]
@@ -323,7 +331,7 @@ class ConvLayer(nn.Sequential):
                 return _conv.conv3x3(input, pk, ec.weight.shape[0], bias=self[1].bias, slope=self[1].negative_slope, gain=self[1].scale, act=True)
             return _conv.conv3x3(input, pk, ec.weight.shape[0], bias=ec.bias, act=False)
         if (isinstance(ec, EqualConv2d) and input.is_cuda and input.dtype == torch.float32 and not torch.is_grad_enabled()
-                and _fused_conv_enabled() and os.environ.get("HAVATAR_CONV_1X1", "0") == "1" and ec.stride == 1 and ec.padding == 0
+                and _fused_conv_enabled() and switches.off("HAVATAR_CONV_1X1") and ec.stride == 1 and ec.padding == 0
                 and _conv.conv1x1_eligible(input, ec.weight)):
             # HIP inference, on request (HAVATAR_CONV_1X1=1): the 1x1 EqualConv2d (FromRGB, conv_out) as a split-fp16 matrix product
             # (hav_gemm_split) instead of rocBLAS' fp32 GEMM.  Measured on SWGAN_unet 512 -> 1024 (K = 64, three layers): 2.74 against 2.70 ms
@@ -338,13 +346,14 @@ class ConvLayer(nn.Sequential):
 
 
 def _fused_haar_enabled():
-    return os.environ.get("HAVATAR_FUSED_HAAR", "1") != "0"
+    return switches.on("HAVATAR_FUSED_HAAR")
 
 
 def _haar_train(x):
     """HAVATAR_HAAR_TRAIN=1 (read at the call), a float32 HIP tensor, grad mode on: the transforms run as the one-launch autograd nodes of
     native/train_ops.py (HaarDwt / HaarIdwt / HaarUp2 / HaarDown2) where the shape is eligible.  Unset (the default): today's statements."""
-    return os.environ.get("HAVATAR_HAAR_TRAIN", "0") == "1" and x.is_cuda and x.dtype == torch.float32 and torch.is_grad_enabled()
+    from ..native.train_ops import haar_enabled
+    return haar_enabled() and x.is_cuda and x.dtype == torch.float32 and torch.is_grad_enabled()
 
 
 def _haar_bank(mod, ks):
@@ -534,7 +543,7 @@ class StyledConv(nn.Module):
             return _conv.fused_block(input, self.conv.weight[0], self.conv.scale, s=s, d=d, noise=noise, noise_weight=self.noise.weight,
                                      bias=self.activate.bias, slope=self.activate.negative_slope, gain=self.activate.scale, act=True)
         if (input.is_cuda and input.dtype == torch.float32 and torch.is_grad_enabled() and self.conv.fused_upconv_ok(input)
-                and os.environ.get("HAVATAR_HIP_TRAIN", "1") != "0" and _conv.upconv_block_eligible(input, self.conv.weight[0])):
+                and _hip_train() and _conv.upconv_block_eligible(input, self.conv.weight[0])):
             # HIP training, up-sampling 3x3: the whole block as one autograd node (native/conv.py::_UpConvBlock)
             s, d = self.conv.style_vectors(style)
             if noise is None:
@@ -582,7 +591,7 @@ class ToRGB(nn.Module):
                 up = train_ops.haar_up2(skip, _haar_bank(self.iwt, (self.iwt.ll, self.iwt.lh, self.iwt.hl, self.iwt.hh)), self.upsample.kernel,
                                         _haar_bank(self.dwt, (self.dwt.ll, self.dwt.lh, self.dwt.hl, self.dwt.hh)))
             skip = up if up is not None else (self.dwt(self.upsample(self.iwt(skip))) if self.use_wt else self.upsample(skip))
-        if self.conv._hip_inference(input) and os.environ.get("HAVATAR_FUSED_TORGB", "1") != "0":
+        if self.conv._hip_inference(input) and switches.on("HAVATAR_FUSED_TORGB"):
             # HIP inference: modulation, the 1x1 convolution, bias and skip add in one pass over the activations (hav_torgb) instead of
             # x * s, MIOpen's GEMM between NHWC transposes, and two adds
             from ..native import fused
@@ -599,7 +608,7 @@ def _prefetch_styles(owner, pairs, latent):
     (hav_style_demod_batched) -- they depend only on the latent.  pairs: [(ModulatedConv2d, index into latent[:, i])].  Each layer
     picks its pair up in style_vectors(); anything the batched kernel does not take falls back to the per-layer launch."""
     if not (latent.is_cuda and latent.dtype == torch.float32 and not torch.is_grad_enabled()
-            and os.environ.get("HAVATAR_STYLE_BATCH", "1") != "0"):
+            and switches.on("HAVATAR_STYLE_BATCH")):
         return
     from ..native import fused
     entries = []
@@ -640,7 +649,7 @@ def _run_style(style, z):
     layers as ONE launch (hav_style_mlp) instead of 5 + 2 n launch-bound ones at the head of the generator's chain; the blob of scaled,
     transposed weights is cached per weights epoch.  Anything else: the module itself."""
     if (z.is_cuda and z.dtype == torch.float32 and z.dim() == 2 and not torch.is_grad_enabled()
-            and os.environ.get("HAVATAR_STYLE_MLP", "1") != "0" and isinstance(style, nn.Sequential) and len(style) >= 2
+            and switches.on("HAVATAR_STYLE_MLP") and isinstance(style, nn.Sequential) and len(style) >= 2
             and isinstance(style[0], PixelNorm)):
         layers = list(style)[1:]
         D = layers[0].weight.shape[0] if isinstance(layers[0], EqualLinear) else 0

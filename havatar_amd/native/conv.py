@@ -6,11 +6,10 @@ operands (libhavatar_hip.so: hav_conv3x3_*, hav_gemm_*, hav_upconv_finish; inclu
 HIP float32 tensors only; no fallback in here -- the `*eligible()` predicates tell the caller whether a shape is supported, otherwise
 it keeps its MIOpen route."""
 import ctypes as C
-import os
 
 import torch
 
-from .. import _lib
+from .. import _lib, switches
 
 
 def _p(t):
@@ -27,14 +26,14 @@ def _stream(device):
 
 
 def _autoscale_default():
-    return os.environ.get("HAVATAR_CONV_AUTOSCALE", "1") != "0"
+    return switches.on("HAVATAR_CONV_AUTOSCALE")
 
 
 # Development aid (tools/graph_anomaly_hunt.py, tests/test_harness.py): is-finite flags per operand / result of the wrappers below, evaluated
 # INSIDE a captured step at every replay.  HAVATAR_NAN_TRACE=1: torch.isfinite(t).all() -- two ATen launches and two temporaries per tensor in
 # the graph's memory pool.  HAVATAR_NAN_TRACE=2 (what the tests use): one hav_debug_nonfinite launch per tensor into a flag buffer that is
 # allocated OUTSIDE any graph pool -- no temporaries; the buffer is zeroed by nan_trace_reset() before a step / replay.
-_NAN_MODE = int(os.environ.get("HAVATAR_NAN_TRACE", "0") or 0)
+_NAN_MODE = int(switches.choice("HAVATAR_NAN_TRACE") or 0)
 _NAN_TRACE = [] if _NAN_MODE else None
 _NAN_BUF = {}          # device -> int32 flag buffer (mode 2)
 _NAN_BUF_WORDS = 8192
@@ -279,7 +278,7 @@ def wgrad_s2_eligible(S, L):
         return False
     B, M, H, W = S.shape
     N = L.shape[1]
-    if L.shape[0] != B or tuple(L.shape[2:]) != (2 * H + 1, 2 * W + 1) or os.environ.get("HAVATAR_S2_WGRAD", "1") == "0":
+    if L.shape[0] != B or tuple(L.shape[2:]) != (2 * H + 1, 2 * W + 1) or not switches.on("HAVATAR_S2_WGRAD"):
         return False
     if W < 16:          # the small-map kernel (4^2 / 8^2 layers): plain fp32, its operand rows must fit in LDS
         return M % 16 == 0 and N % 16 == 0 and (16 * B * H * W + 16 * ((B * (2 * H + 1) * (2 * W + 1)) | 1)) * 4 <= 64 * 1024
@@ -336,14 +335,14 @@ class _Conv3x3Split(torch.autograd.Function):
             return gx, gw
         g = g.contiguous()
         gx = None
-        if need_x and os.environ.get("HAVATAR_CONV_BWD", "1") != "0":
+        if need_x and switches.on("HAVATAR_CONV_BWD"):
             # dL/dx is itself a 3x3 / stride 1 / padding 1 convolution of g with the transposed, flipped filters: the same kernel
             wt = w.flip(2, 3).transpose(0, 1).contiguous()
             if eligible(g, wt):
                 gx = conv3x3(g, pack(wt, 1.0), wt.shape[0], act=False, autoscale=True)     # gradients are ~1e-6: see hav_absmax
                 need_x = False
         gw = None
-        if need_w and os.environ.get("HAVATAR_CONV_WGRAD", "1") != "0" and wgrad_eligible(g, x):
+        if need_w and switches.on("HAVATAR_CONV_WGRAD") and wgrad_eligible(g, x):
             gw = wgrad3x3(g, x)          # the weight gradient on the split-fp16 path too (MIOpen: fp32 igemm_wrw + NHWC transposes)
             need_w = False
         if not (need_x or need_w):
@@ -363,7 +362,7 @@ def block_eligible(x, weight):
     if not eligible(x, weight):
         return False
     Cout, Cin = weight.shape[:2]
-    return Cin % 64 == 0 and Cout % 64 == 0 and os.environ.get("HAVATAR_FUSED_BLOCK", "1") != "0"
+    return Cin % 64 == 0 and Cout % 64 == 0 and switches.on("HAVATAR_FUSED_BLOCK")
 
 
 class _FusedConvBlock(torch.autograd.Function):
@@ -473,7 +472,7 @@ class _S2ConvBlock(torch.autograd.Function):
     def forward(ctx, x, W, bias, fir, scale, slope, gain, act, padding, fpad):
         from ..model.op.upfirdn2d import upfirdn2d as _ufd
         xb = _ufd(x, fir, pad=fpad) if fir is not None else x
-        if os.environ.get("HAVATAR_S2_TRAIN_FWD", "kernel") == "aten":          # (A/B switch: the forward on ATen / MIOpen)
+        if switches.choice("HAVATAR_S2_TRAIN_FWD") == "aten":          # (A/B switch: the forward on ATen / MIOpen)
             y = torch.nn.functional.conv2d(xb, W * scale, stride=2, padding=padding)
             if bias is not None:
                 y = y + bias.view(1, -1, 1, 1)
@@ -528,7 +527,7 @@ class _S2ConvBlock(torch.autograd.Function):
         if need[0]:
             wt = W.transpose(0, 1).contiguous()          # [Cin,Cout,3,3]: as an up-sampling layer's parameter it maps Cout -> Cin channels
             fused = (fir is not None and tuple(fir.shape) == (4, 4) and tuple(fpad) in ((2, 2), (2, 2, 2, 2)) and padding == 0
-                     and tuple(xshape[2:]) == (2 * Ho, 2 * Wo) and upconv_eligible(gc, wt) and os.environ.get("HAVATAR_S2_DGRAD", "1") != "0")
+                     and tuple(xshape[2:]) == (2 * Ho, 2 * Wo) and upconv_eligible(gc, wt) and switches.on("HAVATAR_S2_DGRAD"))
             if fused:
                 gx = upconv3x3(gc, pack_upconv(wt, scale), Cin, fir.flip(0, 1), act=False, autoscale=True)          # gradient-sized: see hav_absmax
             else:
@@ -616,7 +615,7 @@ def upconv3x3(x, packed, Cout, fir, s=None, d=None, noise=None, noise_weight=Non
 def upconv_block_eligible(x, weight):
     """x [B,Cin,H,W], weight [Cout,Cin,3,3]: shapes whose forward (hav_gemm_split + hav_upconv_finish) runs on this library's kernels; the
     data gradient does too where _upconv_dgrad_on_s2 says so."""
-    return upconv_eligible(x, weight) and os.environ.get("HAVATAR_FUSED_UPBLOCK", "1") != "0"
+    return upconv_eligible(x, weight) and switches.on("HAVATAR_FUSED_UPBLOCK")
 
 
 def _upconv_dgrad_on_s2(x, weight):

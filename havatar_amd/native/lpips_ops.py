@@ -10,19 +10,17 @@ HIP float32 tensors only; no fallback in here -- conv_relu_eligible() tells the 
 
 HAVATAR_LPIPS (read at the call): 0 = the ATen statement throughout; 1 = the nodes; unset = DEFAULT below (DESIGN.md 7.8 holds the
 measurement that decided it)."""
-import os
-
 import torch
 from torch.autograd.function import once_differentiable
 
-from .. import _lib
+from .. import _lib, switches
 from . import conv as nconv
 
-DEFAULT = "1"
+DEFAULT = switches.default("HAVATAR_LPIPS")
 
 
 def enabled():
-    return os.environ.get("HAVATAR_LPIPS", DEFAULT) != "0"
+    return switches.on("HAVATAR_LPIPS")
 
 
 def _need_hip(*ts):

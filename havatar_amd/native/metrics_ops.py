@@ -6,20 +6,18 @@ havatar_amd.metrics decides which calls come this way (eligible()) and states th
 
 HAVATAR_METRICS (read at the call): 0 = the ATen statement throughout; unset / 1 = these entries for eligible HIP tensors (DESIGN.md 7.9 holds the
 measurement that decided the default)."""
-import os
-
 import torch
 
-from .. import _lib
+from .. import _lib, switches
 from .conv import _p, _stream
 
-DEFAULT = "1"
+DEFAULT = switches.default("HAVATAR_METRICS")
 WIN = 11                       # window taps; the map is [H - WIN + 1, W - WIN + 1]
 TILE_H, TILE_W = 32, 32        # map elements per workgroup (MET_TH, MET_TW of csrc/hav_metrics.hip)
 
 
 def enabled():
-    return os.environ.get("HAVATAR_METRICS", DEFAULT) != "0"
+    return switches.on("HAVATAR_METRICS")
 
 
 def eligible(a, b):

@@ -2,13 +2,12 @@
 radiance MLP in predict_and_render_radiance -- skinning field + box warp + tri-plane gather + positional encoding on one side,
 volume_render_radiance_field on the other.  HIP float32 tensors only; there is no fallback in here."""
 import ctypes as C
-import os
 
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from .. import _lib
+from .. import _lib, switches
 
 # Under torch.autocast these nodes compute in fp32 like everywhere else: inputs are cast to fp32 and autocast is off inside forward AND backward
 # (without this, torch.mm inside Conv3dSmall.forward would return bf16 under autocast while backward, which runs outside it, multiplies a
@@ -46,7 +45,7 @@ def _field_params(pts, planes_cl, vol, boxes):
 
 def deterministic():
     """HAVATAR_DETERMINISTIC=1: the training-side scatters sum in 64-bit fixed point (bit-reproducible gradients; ~1 ms per step)."""
-    return os.environ.get("HAVATAR_DETERMINISTIC", "0") == "1"
+    return switches.off("HAVATAR_DETERMINISTIC")
 
 
 class FieldInputs(Function):
@@ -264,7 +263,7 @@ def composite_long_eligible(S, rf_like):
 
 def composite_long_enabled():
     """HAVATAR_COMPOSITE_LONG=1 (read at the call): a training step with 65-128 samples per pass stays on the native route"""
-    return os.environ.get("HAVATAR_COMPOSITE_LONG", "0") == "1"
+    return switches.off("HAVATAR_COMPOSITE_LONG")
 
 
 def resample_depths(z, weights, num_fine, zeta=None, return_samples=False):
@@ -433,7 +432,7 @@ def conv3d_small_eligible(x, conv):
         return False          # anything else stays on nn.Conv3d (a non-fp32 weight made Conv3dSmall raise instead of falling back)
     return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 5 and x.shape[0] == 1 and x.shape[2] == x.shape[3] == x.shape[4] and x.shape[2] <= 8
             and tuple(conv.kernel_size) == (3, 3, 3) and tuple(conv.padding) == (1, 1, 1) and tuple(conv.stride) == (1, 1, 1)
-            and tuple(conv.dilation) == (1, 1, 1) and conv.groups == 1 and os.environ.get("HAVATAR_CONV3D_SMALL", "1") != "0")
+            and tuple(conv.dilation) == (1, 1, 1) and conv.groups == 1 and switches.on("HAVATAR_CONV3D_SMALL"))
 
 
 def conv3d_small(x, conv):
@@ -755,7 +754,7 @@ def _flipped(k, mul=1.0):
 
 def haar_enabled():
     """HAVATAR_HAAR_TRAIN=1 (read at the call): the wavelet transforms of both stage-two networks run as one-launch autograd nodes"""
-    return os.environ.get("HAVATAR_HAAR_TRAIN", "0") == "1"
+    return switches.off("HAVATAR_HAAR_TRAIN")
 
 
 def _haar_tensor(x):
@@ -921,7 +920,7 @@ def haar_down2(x, ki4, fir, kd4, scale=1.0):
 def s2_loss_enabled():
     """harness/train_hd.py::joint_step takes Stage2ImageLoss for its image-space losses where the tensors are eligible (the default: the node is
     faster than the statement at both measured sizes); HAVATAR_S2_LOSS=0 selects the ATen statement.  Read at the call."""
-    return os.environ.get("HAVATAR_S2_LOSS", "1") != "0"
+    return switches.on("HAVATAR_S2_LOSS")
 
 
 def stage2_image_loss_statement(render, mask, gt_lr_img, fake_img, gt_hr_img, gt_lr_mask, rgb_loss="mse"):

@@ -6,14 +6,13 @@ the MFMA-fragment-ordered weight blob (re-packed only when the weights change) a
 `hav_render_rays` on torch's current HIP stream.
 """
 import ctypes as C
-import os
 
 import torch
 
-from . import _lib
+from . import _lib, switches
 from .graph import weights_epoch
 
-_DEBUG_SYNC = os.environ.get("HAVATAR_DEBUG_SYNC", "0") == "1"
+_DEBUG_SYNC = switches.off("HAVATAR_DEBUG_SYNC")
 
 
 def _ptr(t):
@@ -42,7 +41,7 @@ def _chk_f32_cuda(name, t, allow_none=False):
 # NARROWER than the reference's fp32, the fastest); "f32": exact fp32 MFMA (an fmaf chain).
 MLP_MODES = {"mx": _lib.HAV_MLP_SPLIT_F16_MX, "split": _lib.HAV_MLP_SPLIT_BF16, "bf16": _lib.HAV_MLP_SPLIT_BF16, "half": _lib.HAV_MLP_SPLIT_F16,
              "fp16": _lib.HAV_MLP_SPLIT_F16, "f32": _lib.HAV_MLP_F32}
-DEFAULT_MLP = "mx"
+DEFAULT_MLP = switches.default("HAVATAR_MLP")
 
 
 class RayMarcher:
@@ -61,16 +60,16 @@ class RayMarcher:
         self.rng_offset = 0
         self.seed = 0x9E3779B97F4A7C15
         # arithmetic of the two dense layers (include/havatar.h): MLP_MODES / DEFAULT_MLP below
-        self.mlp_mode = MLP_MODES.get(os.environ.get("HAVATAR_MLP", DEFAULT_MLP), MLP_MODES[DEFAULT_MLP])
+        self.mlp_mode = MLP_MODES.get(switches.choice("HAVATAR_MLP"), MLP_MODES[DEFAULT_MLP])
         # fine-pass cache: re-use the coarse pass's field values for the even coarse samples the merged list repeats
-        self.fine_cache = os.environ.get("HAVATAR_FINE_CACHE", "1") != "0"
+        self.fine_cache = switches.on("HAVATAR_FINE_CACHE")
         self._workspace = None
         # per-call switches of the library (HavRenderParams.flags).  The A/B environment variables are read HERE, once per
         # marcher; the library itself reads no environment on the launch path.
         self.flags = 0
-        if os.environ.get("HAV_MARCH", "")[:1] == "p":
+        if switches.choice("HAV_MARCH")[:1] == "p":
             self.flags |= _lib.HAV_FLAG_PAIR_KERNEL
-        self.flags |= {"cache": _lib.HAV_FLAG_FINE_CACHE, "recompute": _lib.HAV_FLAG_FINE_RECOMPUTE}.get(os.environ.get("HAV_FINE", ""), 0)
+        self.flags |= {"cache": _lib.HAV_FLAG_FINE_CACHE, "recompute": _lib.HAV_FLAG_FINE_RECOMPUTE}.get(switches.choice("HAV_FINE"), 0)
         self._status = None          # device word the library ORs HAV_STATUS_* bits into
         self.last_variant = None     # name of the kernel instantiation the last render() launched
 
