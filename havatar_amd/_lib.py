@@ -128,7 +128,9 @@ def lib():
                        ("hav_relu_mask_bwd", [vp] * 4 + [i32, i32, i64, vp]),
                        ("hav_image_metrics_blocks", [i32] * 4),
                        ("hav_image_metrics_f32", [vp] * 5 + [i32] * 4 + [f32, vp]),
-                       ("hav_image_metrics_u8", [vp] * 5 + [i32] * 3 + [vp])):
+                       ("hav_image_metrics_u8", [vp] * 5 + [i32] * 3 + [vp]),
+                       ("hav_ssim_grad_blocks", [i32] * 4),
+                       ("hav_ssim_loss_bwd_f32", [vp] * 5 + [i32] * 4 + [f32, vp])):
         try:
             fn = getattr(L, name)
         except AttributeError:

@@ -9,6 +9,9 @@ first/second-order autograd.  Validation frames are rendered through the fused k
 LPIPS (patch_rgb) needs the `lpips` package and its VGG weights; when they are absent the harness refuses to start unless
 `--percep none` is given, which drops that one term and says so.  `--percep native --percep-vgg PATH --percep-lin PATH` takes the term from
 this package's own module (model/lpips.py: the same function on this library's kernels, no `lpips` / torchvision import).
+Added terms and scalars, all off by default: `--ssim-weight W` adds W * (1 - SSIM) of the patch (metrics.ssim_loss: 11-tap Gaussian window;
+needs experiment.patch_rgb, because random rays are not an image), `--val-metrics` logs validation/ssim (and validation/lpips when a perceptual
+module is loaded) of the validation frame.
 """
 import argparse
 import datetime
@@ -36,6 +39,16 @@ def lpips_loss(img0, img1, lpips_fn):
     return lpips_fn.forward(img0, img1).mean()
 
 
+def patch_ssim_loss(patch, target):
+    """[B,s*s,3] rays of a square patch -> 1 - mean SSIM of the [B,3,s,s] pair (metrics.ssim_loss; the views are permuted, not copied)"""
+    from .. import metrics
+    s = int(round(patch.shape[1] ** 0.5))
+    if s * s != patch.shape[1] or s < metrics.WIN:
+        raise RuntimeError("the SSIM term needs the rays of a square patch of at least %d x %d pixels (experiment.patch_rgb), got %d rays"
+                           % (metrics.WIN, metrics.WIN, patch.shape[1]))
+    return metrics.ssim_loss(patch.reshape(patch.shape[0], s, s, 3).permute(0, 3, 1, 2), target.reshape(patch.shape[0], s, s, 3).permute(0, 3, 1, 2))
+
+
 def skin_weight_smoothness(trainer):
     """Mean absolute 6-neighbour difference of the second blend-weight channel (train_avatar.py:123-129)."""
     net = trainer.headpose_skin_net
@@ -58,8 +71,9 @@ def step_inputs(idx, batch, device):
     return inp, batch["mv_rays_gt_color"].to(device), mv_rays[..., -1:]
 
 
-def training_loss(trainer, cfg, inp, target, ray_mask, rgb_loss_func, percep_loss_fn=None):
-    """One forward of the step and its scalar loss (train_avatar.py:121-146).  Returns (loss, parts, psnr)."""
+def training_loss(trainer, cfg, inp, target, ray_mask, rgb_loss_func, percep_loss_fn=None, ssim_weight=0.0):
+    """One forward of the step and its scalar loss (train_avatar.py:121-146).  Returns (loss, parts, psnr).  ssim_weight: adds that times
+    metrics.ssim_loss of the [B,3,s,s] patch (parts["patch_ssim_loss"]); the rays must be a square patch (experiment.patch_rgb)."""
     rgb_coarse, _, acc_coarse, weights, rgb_fine, _, acc_fine, latent_code_loss = trainer(**inp)
     sw_grad_loss = skin_weight_smoothness(trainer)
     if rgb_coarse.is_cuda:
@@ -80,6 +94,9 @@ def training_loss(trainer, cfg, inp, target, ray_mask, rgb_loss_func, percep_los
     if rgb_fine is not None:
         loss = loss + (parts["fine_loss"] + mw * parts["mask_fine_loss"])
     loss = loss + latent_code_loss + sw_grad_loss * 1e-4
+    if ssim_weight:
+        parts["patch_ssim_loss"] = patch_ssim_loss(rgb_coarse[..., :3] if rgb_fine is None else rgb_fine[..., :3], target[..., :3])
+        loss = loss + ssim_weight * parts["patch_ssim_loss"]
     parts.update(code_loss=latent_code_loss, sw_grad_loss=sw_grad_loss)
     best = rgb_coarse if rgb_fine is None else rgb_fine
     mse = F.mse_loss(best[..., :3], target[..., :3]).detach()
@@ -142,8 +159,9 @@ class StepRunner:
     """forward + backward + optimiser update of one batch; eager for the first `eager_steps` calls (solver selection, lazy
     optimiser state) and for odd batch shapes, one hipGraph replay otherwise."""
 
-    def __init__(self, trainer, cfg, optimizer, rgb_loss_func, percep_loss_fn=None, graph=False, eager_steps=2):
+    def __init__(self, trainer, cfg, optimizer, rgb_loss_func, percep_loss_fn=None, graph=False, eager_steps=2, ssim_weight=0.0):
         self.trainer, self.cfg, self.optimizer, self.rgb_loss_func, self.percep = trainer, cfg, optimizer, rgb_loss_func, percep_loss_fn
+        self.ssim_weight = float(ssim_weight)
         self.graph, self.eager_left, self.graphed, self.side = graph, eager_steps, None, None
         if deterministic_requested():
             enable_determinism()
@@ -163,7 +181,7 @@ class StepRunner:
     def _loss(self, target, ray_mask, **inp):
         t = self.trainer
         full = dict(inp, mode="train", render_full_img=False)
-        loss, parts, mse = training_loss(t, self.cfg, full, target, ray_mask, self.rgb_loss_func, self.percep)
+        loss, parts, mse = training_loss(t, self.cfg, full, target, ray_mask, self.rgb_loss_func, self.percep, self.ssim_weight)
         return loss, dict(parts, _mse=mse)
 
     def __call__(self, inp, target, ray_mask):
@@ -189,7 +207,8 @@ class StepRunner:
             return loss, parts, mse2psnr(aux["_mse"].item())
         self.eager_left -= 1
         if not self.graph:
-            loss, parts, psnr = training_loss(self.trainer, self.cfg, inp, target, ray_mask, self.rgb_loss_func, self.percep)
+            loss, parts, psnr = training_loss(self.trainer, self.cfg, inp, target, ray_mask, self.rgb_loss_func, self.percep,
+                                              self.ssim_weight)
             loss.backward()
             self.optimizer.step()
             self.optimizer.zero_grad()
@@ -203,7 +222,8 @@ class StepRunner:
         self.side.wait_stream(cur)
         with torch.cuda.stream(self.side):
             self.optimizer.zero_grad(set_to_none=True)
-            loss, parts, psnr = training_loss(self.trainer, self.cfg, inp, target, ray_mask, self.rgb_loss_func, self.percep)
+            loss, parts, psnr = training_loss(self.trainer, self.cfg, inp, target, ray_mask, self.rgb_loss_func, self.percep,
+                                              self.ssim_weight)
             loss.backward()
             self.optimizer.step()
             self.optimizer.zero_grad(set_to_none=True)
@@ -242,6 +262,25 @@ def validate(trainer, cfg, val_batch, img_h, img_w, device, rgb_loss_func):
     return img, target, loss.item(), mse2psnr(F.mse_loss(img, target).item())
 
 
+def validation_metrics(img, target, device, percep_loss_fn=None):
+    """{"ssim"} (+ {"lpips"} with a perceptual module) of the validation frames [V,H,W,3], clamped to [0,1] as the PNG is, on `device`"""
+    from .. import metrics
+    a, b = img.clamp(0, 1).to(device), target.clamp(0, 1).to(device)
+    with torch.no_grad():
+        out = {"ssim": metrics.ssim(a.permute(0, 3, 1, 2), b.permute(0, 3, 1, 2)).mean().item()}
+        if percep_loss_fn is not None:
+            out["lpips"] = lpips_loss(a, b, percep_loss_fn).item()
+    return out
+
+
+def make_writer(logdir):
+    try:
+        from torch.utils.tensorboard import SummaryWriter
+        return SummaryWriter(logdir)
+    except Exception:  # tensorboard is optional here
+        return _NullWriter()
+
+
 class _NullWriter:
     def add_scalar(self, *a, **k):
         pass
@@ -261,6 +300,10 @@ def parse_args(argv=None):
     p.add_argument("--percep-vgg", type=str, default="", help="--percep native: torchvision VGG16 weights (vgg16-*.pth)")
     p.add_argument("--percep-lin", type=str, default="", help="--percep native: the lpips package's linear layers (weights/v0.1/vgg.pth)")
     p.add_argument("--max-steps", type=int, default=0, help="stop after this many optimisation steps (0 = experiment.train_iters)")
+    p.add_argument("--ssim-weight", type=float, default=0.0,
+                   help="adds this times (1 - SSIM) of the patch to the loss (metrics.ssim_loss); needs experiment.patch_rgb")
+    p.add_argument("--val-metrics", action="store_true", default=False,
+                   help="log validation/ssim (and validation/lpips with a perceptual module) of the validation frame")
     return p.parse_args(argv)
 
 
@@ -273,6 +316,9 @@ def main(argv=None, device=None):
     np.random.seed(seed)
     torch.manual_seed(seed)
     device = torch.device(device if device is not None else "cuda")
+    if args.ssim_weight and not cfg.experiment.patch_rgb:
+        raise RuntimeError("--ssim-weight needs experiment.patch_rgb: SSIM is a function of an image, and the random rays of a step without "
+                           "patch_rgb are not one")
     percep_loss_fn = None
     if cfg.experiment.patch_rgb and args.percep == "lpips":
         try:
@@ -295,13 +341,11 @@ def main(argv=None, device=None):
     val_data = enumerate(val_loader)
     trainer = Trainer(cfg, len(train_loader.dataset)).to(device)
     use_graph = graph_training_enabled(device, percep_loss_fn)
+    if use_graph and args.ssim_weight and not switches.on("HAVATAR_METRICS"):
+        use_graph = False          # the ATen statement of the SSIM term uploads its window from the host at every call: not capturable
     optimizer = make_optimizer(cfg, trainer, use_graph)
     os.makedirs(args.logdir, exist_ok=True)
-    try:
-        from torch.utils.tensorboard import SummaryWriter
-        writer = SummaryWriter(args.logdir)
-    except Exception:  # tensorboard is optional here
-        writer = _NullWriter()
+    writer = make_writer(args.logdir)
     with open(os.path.join(args.logdir, "config_%s.tar.yml" % now.strftime("%Y_%m_%d_%H_%M_%S")), "w") as f:
         f.write(cfg.dump())
     start_iter = -1
@@ -315,7 +359,7 @@ def main(argv=None, device=None):
         trainer.headpose_skin_net.pretrain_wc(num_iter=switches.integer("HAVATAR_PRETRAIN_WC"), vol_thr=cfg.models.coarse.Head_bounding)
     i, steps_done = start_iter, 0
     loss, psnr = None, None
-    run_step = StepRunner(trainer, cfg, optimizer, rgb_loss_func, percep_loss_fn, graph=use_graph)
+    run_step = StepRunner(trainer, cfg, optimizer, rgb_loss_func, percep_loss_fn, graph=use_graph, ssim_weight=args.ssim_weight)
     while i < cfg.experiment.train_iters:
         trainer.train()
         t0 = time.time()
@@ -348,6 +392,9 @@ def main(argv=None, device=None):
                         vb = next(val_data)
                     img, target_img, vloss, vpsnr = validate(trainer, cfg, vb[1], val_loader.dataset.img_h, val_loader.dataset.img_w, device, rgb_loss_func)
                 writer.add_scalar("validation/psnr", vpsnr, i)
+                if args.val_metrics:
+                    for k, v in validation_metrics(img, target_img, device, percep_loss_fn).items():
+                        writer.add_scalar("validation/" + k, v, i)
                 imgio.imwrite_rgb(os.path.join(args.logdir, "val_%05d.png" % i),
                                   (torch.cat([img[0], target_img[0]], 1).clamp(0, 1) * 255).round().byte().numpy())
                 print("Validation loss: %06f Validation PSNR: %06f" % (vloss, vpsnr))

@@ -6,8 +6,8 @@ Same flags, optimisers (:117-122), per-iteration statements (:181-303, `joint_st
 g_optim, d_optim, nerf_render, g, d, g_ema, latent_codes`), both load modes (:137-159).  Added flags: `--gan-ckpt` (the reference hard-codes
 pretrained_models/img_translation.ckpt, :144), `--percep {lpips,none}` (LPIPS needs the `lpips` package and its VGG weights; without them the
 harness refuses to start unless `none` is given, which drops the 0.1 * LPIPS term and says so; `--percep native --percep-vgg PATH
---percep-lin PATH` takes the term from this package's own module, model/lpips.py, with no `lpips` / torchvision import), `--iters` /
-`--batch` for short runs.
+--percep-lin PATH` takes the term from this package's own module, model/lpips.py, with no `lpips` / torchvision import), `--ssim-weight W`
+(adds W * (1 - SSIM(fake, gt)), metrics.ssim_loss; default 0: no such term), `--iters` / `--batch` for short runs.
 What is different by design: scalars go to tensorboard only if it is installed (and to stdout every experiment.print_every iterations),
 there is no code tarball and no progress bar, the sample image is written through imgio, `latest.pt` is also written after the run's last
 iteration, and `--continue-training` continues the iteration count from the checkpoint's `iter` (the reference has that line commented out
@@ -23,7 +23,7 @@ import torch
 import torch.nn.functional as F
 import yaml
 
-from .. import switches
+from .. import metrics, switches
 from ..dataloader import imgio
 from ..dataloader.dataloaderSR import Loader
 from ..model.nerf_trainer import Trainer
@@ -63,7 +63,7 @@ def step_inputs(batch, device, render_size, gen_size):
     return inp, gt_hr_img, gt_lr_mask
 
 
-def joint_step(i, batch, nets, optims, cfg, su_args, percep=None, util=None, probe=None, aux=None):
+def joint_step(i, batch, nets, optims, cfg, su_args, percep=None, util=None, probe=None, aux=None, ssim_weight=0.0):
     """One iteration of the joint NeRF + GAN training, the reference's statements in the reference's order (train_avatarHD.py:186-303):
       1. no-grad render and fake image (the fused march kernel on HIP tensors)           :211-217
       2. the discriminator's logistic step                                                :219-231
@@ -72,7 +72,8 @@ def joint_step(i, batch, nets, optims, cfg, su_args, percep=None, util=None, pro
       5. rgb loss, code loss, mask BCE                                                    :246-254
       6. the generator's forward on render[:, 3:]                                         :257-260
       7. the non-saturating loss through the frozen discriminator, times gan_loss_weight  :262-266
-      8. HR L1 (+ 0.1 * LPIPS when `percep` is given)                                     :268-274
+      8. HR L1 (+ 0.1 * LPIPS when `percep` is given; + ssim_weight * (1 - SSIM(fake, gt)), metrics.ssim_loss, when ssim_weight is
+         not 0 -- not in the reference)                                                   :268-274
       9. one backward; 10. g_optim.step(), nerf_optimizer.step()                          :276-280
      11. accumulate(g_ema, generator, 0.5 ** (32 / 10000))                                :303
     The path-length block of the reference (:285-301) is dead code there (`if False`) and is not here.  Random numbers are consumed as the
@@ -159,6 +160,10 @@ def joint_step(i, batch, nets, optims, cfg, su_args, percep=None, util=None, pro
         percep_loss = lpips_loss(fake_img, gt_hr_img, percep)
         g_loss = g_loss + percep_loss * 0.1
         scalars["percep_loss"] = percep_loss
+    if ssim_weight:
+        ssim_term = metrics.ssim_loss(fake_img, gt_hr_img)
+        g_loss = g_loss + ssim_weight * ssim_term
+        scalars["ssim_loss"] = ssim_term
     probe("g_forward")
 
     # 9-11
@@ -280,6 +285,7 @@ def parse_args(argv=None):
                         "(no lpips package / weights)")
     p.add_argument("--percep-vgg", type=str, default="", help="--percep native: torchvision VGG16 weights (vgg16-*.pth)")
     p.add_argument("--percep-lin", type=str, default="", help="--percep native: the lpips package's linear layers (weights/v0.1/vgg.pth)")
+    p.add_argument("--ssim-weight", type=float, default=0.0, help="adds this times (1 - SSIM(fake, gt)) to the generator's loss (metrics.ssim_loss)")
     p.add_argument("--iters", type=int, default=0, help="run iterations up to this one, exclusive (0 = styleUnet_args.iter)")
     p.add_argument("--batch", type=int, default=0, help="batch size (0 = styleUnet_args.batch)")
     return p.parse_args(argv)
@@ -336,7 +342,7 @@ def main(argv=None, device=None):
     i = start_iter
     for i in range(start_iter + 1, su_args.iter):
         aux = {}
-        s = joint_step(i, next(loader), nets, optims, cfg, su_args, percep, aux=aux)
+        s = joint_step(i, next(loader), nets, optims, cfg, su_args, percep, aux=aux, ssim_weight=args.ssim_weight)
         for k, v in s.items():
             writer.add_scalar("train/" + k, v, i)
         if i % cfg.experiment.print_every == 0 or i == last:

@@ -8,14 +8,16 @@ give.  PSNR = 10 log10(L^2 / mse) over all elements, inf at mse 0.
 Pairs are float [B,C,H,W] or uint8 [B,H,W,3] (channels-last, what a PNG is; scored as x / 255 with L = 1).  Routing: float32 and uint8 HIP
 tensors take csrc/hav_metrics.hip (native/metrics_ops.py); everything else -- CPU tensors, other dtypes, tensors that need a gradient,
 HAVATAR_METRICS=0 -- takes the ATen statement of the same definition (depthwise conv2d, two passes), in float64 for uint8 and CPU pairs and in
-the input dtype for floating HIP tensors.  The native route carries no autograd (an SSIM training loss is out of scope)."""
+the input dtype for floating HIP tensors.  These functions carry no autograd on the native route; the training loss is ssim_loss(): for a
+float32 HIP pair whose first image needs a gradient it takes the node of native/ssim_ops.py (csrc/hav_ssim_loss.hip: the same forward bits,
+float64 gradient kernels), otherwise the statement under autograd."""
 import json
 import math
 
 import torch
 import torch.nn.functional as F
 
-from .native import metrics_ops
+from .native import metrics_ops, ssim_ops
 
 WIN, SIGMA, K1, K2 = metrics_ops.WIN, 1.5, 0.01, 0.03
 DEFINITION = {"ssim": "Wang et al. 2004, per channel, mean over map and channels", "window": "gaussian, %d taps, separable, normalised to sum 1" % WIN,
@@ -100,6 +102,23 @@ def ssim(a, b, data_range=1.0, return_map=False):
     """[B] mean SSIM per sample; return_map: (that, the map [B,C,H-10,W-10])"""
     s, _, smap = _both(a, b, data_range, return_map)
     return (s, smap) if return_map else s
+
+
+def ssim_loss(pred, target, data_range=1.0):
+    """The scalar 1 - mean_b ssim_b of a float [B,C,H,W] pair, in the pair's dtype, differentiable in pred (and, on the statement route, in
+    target).  Routing: nothing needs a gradient -> ssim(); a float32 HIP pair on one device whose target is a constant, HAVATAR_METRICS on ->
+    the node of native/ssim_ops.py (forward bits of ssim(), float64 gradient kernels); everything else -> the ATen statement under autograd,
+    in float64 for CPU pairs and in the pair's dtype for HIP ones."""
+    if _check_pair(pred, target) == "u8":
+        raise ValueError("metrics: ssim_loss takes float [B,C,H,W] pairs (uint8 carries no gradient), got %s %s" % (pred.dtype, tuple(pred.shape)))
+    if not (torch.is_grad_enabled() and (pred.requires_grad or target.requires_grad)):
+        return (1.0 - ssim(pred, target, data_range).mean()).to(pred.dtype)
+    if (metrics_ops.enabled() and pred.is_cuda and target.is_cuda and pred.device == target.device and pred.dtype == torch.float32
+            and not target.requires_grad):
+        return 1.0 - ssim_ops.ssim_mean(pred, target, data_range).mean()
+    if not pred.is_cuda:
+        return (1.0 - aten_statement(pred.double(), target.double(), data_range)[0].mean()).to(pred.dtype)
+    return 1.0 - aten_statement(pred, target, data_range)[0].mean()
 
 
 def _psnr_of(mse, data_range):

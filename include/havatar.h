@@ -495,6 +495,21 @@ int hav_image_metrics_f32(float* out, double* partials, float* map, const float*
                           float data_range, void* stream);
 int hav_image_metrics_u8(float* out, double* partials, float* map, const uint8_t* a, const uint8_t* b, int B, int H, int W, void* stream);
 
+/* Gradient of the mean SSIM above with respect to its first image (csrc/hav_ssim_loss.hip; added within ABI 8: additive) -- the backward of
+ * the SSIM training loss; the forward value is hav_image_metrics_f32's.  No reference counterpart.
+ *   grad_x [B,C,H,W] float32 = d(sum_b gout[b] ssim_b) / dx, with ssim_b of (x, y, data_range) as defined above and y a constant; every
+ *   element is written exactly once (the buffer needs no initialisation).  x, y [B,C,H,W] contiguous float32; gout [B] float32 on the device.
+ *   ws: 3 B C (H-10) (W-10) doubles of workspace -- the maps dS/dm1, dS/de11, dS/de12 in float64, written by the first launch (a workgroup
+ *   per 32 x 32 map tile) and correlated with the window over the FULL range by the second (a workgroup per 32 x 32 pixel tile).
+ *   Moments, derivative maps and correlation sums are float64, rounded to float32 once at the store.
+ *   hav_ssim_grad_blocks: the workgroups of the two launches together, B C (map tiles + pixel tiles); 0 for sizes the entry refuses.
+ * The same inputs give the same bits on every launch (no atomics).  NULL pointers, sizes < 1, data_range not positive and finite: HAV_EINVAL;
+ * H < 11, W < 11 or more than 2^31 - 1 workgroups in a launch: HAV_EUNSUP; both before any launch.  W % 4 == 0 with 16-byte aligned grad_x, ws,
+ * x, y takes 16-byte accesses, anything else 8-byte (ws) and 4-byte ones.  No allocation, no synchronisation: capturable. */
+int64_t hav_ssim_grad_blocks(int B, int C, int H, int W);
+int hav_ssim_loss_bwd_f32(float* grad_x, double* ws, const float* x, const float* y, const float* gout, int B, int C, int H, int W,
+                          float data_range, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Trilinear x2 up-sampling of a [N,C,D,H,W] float32 volume and its adjoint -- nn.Upsample(scale_factor=2, mode='trilinear',
  * align_corners=False), the first stage of every UpConv3DBlock of the skinning-volume decoder
