@@ -130,7 +130,10 @@ def lib():
                        ("hav_image_metrics_f32", [vp] * 5 + [i32] * 4 + [f32, vp]),
                        ("hav_image_metrics_u8", [vp] * 5 + [i32] * 3 + [vp]),
                        ("hav_ssim_grad_blocks", [i32] * 4),
-                       ("hav_ssim_loss_bwd_f32", [vp] * 5 + [i32] * 4 + [f32, vp])):
+                       ("hav_ssim_loss_bwd_f32", [vp] * 5 + [i32] * 4 + [f32, vp]),
+                       ("hav_iso_blocks", [i32] * 3),
+                       ("hav_iso_classify", [vp] * 3 + [i32] * 3 + [f32, vp]),
+                       ("hav_iso_emit", [vp] * 7 + [i32] * 3 + [f32, C.POINTER(f32), C.POINTER(f32), vp])):
         try:
             fn = getattr(L, name)
         except AttributeError:

@@ -54,6 +54,12 @@ def parse_args(argv=None):
                    "--percep paths) and write <savedir>/metrics.json.")
     p.add_argument("--percep-vgg", type=str, default="", help="--metrics: torchvision VGG16 weights for LPIPS.")
     p.add_argument("--percep-lin", type=str, default="", help="--metrics: lpips linear-layer weights for LPIPS.")
+    p.add_argument("--mesh", action="store_true", help="Extract every frame's density iso-surface (havatar_amd.geometry) and write "
+                   "<savedir>/mesh/<fidx>_<view>.ply with normals and vertex colours.")
+    p.add_argument("--mesh-res", type=int, default=128, help="--mesh: lattice points per axis.")
+    p.add_argument("--mesh-iso", type=float, default=None, help="--mesh: density level of the surface (default: geometry.DEFAULT_ISO).")
+    p.add_argument("--mesh-space", choices=("canonical", "posed"), default="canonical", help="--mesh: the canonical box (pose-free) or the "
+                   "frame's posed box.")
     return p.parse_args(argv)
 
 
@@ -143,9 +149,24 @@ def check_metric_sizes(cfg, split):
                            "photographs" % (out_size, img_res))
 
 
+def frame_mesh(nerf_render, inv_head_T, bidx, args):
+    """--mesh: the mesh of sample bidx of the frames just rendered (their planes are still the trainer's current ones; extraction only reads),
+    as host arrays for write_ply"""
+    from .. import geometry
+    iso = geometry.DEFAULT_ISO if args.mesh_iso is None else args.mesh_iso
+    mesh = geometry.extract_mesh(nerf_render, inv_head_T, res=args.mesh_res, iso=iso, space=args.mesh_space, colors=True, bidx=bidx)
+    return [t.cpu().numpy() for t in mesh]
+
+
 def main(argv=None, device=None, style=None):
+    """Returns the PNG paths; main.mesh_written lists the PLY paths of the last call (empty without --mesh)."""
     args = parse_args(argv)
+    main.mesh_written = []
     os.makedirs(os.path.join(args.savedir, "rgb"), exist_ok=True)
+    if args.mesh:
+        if args.mesh_res < 2:
+            raise RuntimeError("--mesh-res %d: the lattice needs at least 2 points per axis" % args.mesh_res)
+        os.makedirs(os.path.join(args.savedir, "mesh"), exist_ok=True)
     with open(args.config, "r") as f:
         cfg = CfgNode(yaml.load(f, Loader=yaml.FullLoader))
     if args.metrics:
@@ -222,6 +243,10 @@ def main(argv=None, device=None, style=None):
                 name, k = str(int(val_batch["fidx"][b])), int(val_batch["vidx"][0][b])          # ("vidx" is a one-element list per item: collated to [tensor[n]])
                 path = os.path.join(args.savedir, "rgb", f"{name}_{k:02d}.png")
                 written.append(path)
+                if args.mesh:
+                    from ..geometry import write_ply
+                    main.mesh_written.append(os.path.join(args.savedir, "mesh", f"{name}_{k:02d}.ply"))
+                    pending.append(writers.submit(write_ply, main.mesh_written[-1], *frame_mesh(nerf_render, inp["inv_head_T"], b, args)))
                 if device.type != "cuda":
                     arr = to_png_array(gen_img)
                     if scores is not None:

@@ -510,6 +510,37 @@ int64_t hav_ssim_grad_blocks(int B, int C, int H, int W);
 int hav_ssim_loss_bwd_f32(float* grad_x, double* ws, const float* x, const float* y, const float* gout, int B, int C, int H, int W,
                           float data_range, void* stream);
 
+/* Iso-surface of a scalar lattice: marching tetrahedra on the Kuhn subdivision (csrc/hav_isosurface.hip; added within ABI 8: additive) -- the
+ * extractor behind havatar_amd.geometry.isosurface.  No reference counterpart.
+ *   Field: f [D0,D1,D2] contiguous float32, every D >= 2; lattice point (i,j,k) has linear index n = (i D1 + j) D2 + k and position
+ *   origin + (i,j,k) spacing, per axis.  A point is inside iff f > iso (strict; NaN is outside).
+ *   Vertices: point n owns the seven edges n -> n + d, d = (di,dj,dk) in {0,1}^3 \ {0}, numbered e = 4 di + 2 dj + dk - 1.  An owned edge
+ *   whose far end lies in the grid and whose ends differ in inside-ness carries one vertex: with a = f[n], b = f[n+d], t = (iso - a) / (b - a)
+ *   in float32, 0.5 when that is not finite, else clamped to [0,1]; position origin + ((i,j,k) + t d) spacing.  Order: ascending n, then e.
+ *   Triangles: the cube with lower corner n exists when i < D0-1, j < D1-1, k < D2-1.  It splits into six tetrahedra tau = 0..5, one per
+ *   permutation (a1,a2,a3) of the axes in lexicographic order (012, 021, 102, 120, 201, 210), corners c0 = n, c1 = c0 + e_a1, c2 = c1 + e_a2,
+ *   c3 = c2 + e_a3.  With I / O the inside / outside corners in c0..c3 order and (p,q) the vertex on the edge between corners p and q:
+ *     |I| = 1: (I0,O0),(I0,O1),(I0,O2)    |I| = 3: (O0,I0),(O0,I1),(O0,I2)    |I| = 2: (I0,O0),(I0,O1),(I1,O1) then (I0,O0),(I1,O1),(I1,O0)
+ *   and none for |I| = 0 or 4.  A triangle keeps this order or has its last two entries swapped, so that its right-handed normal -- taken
+ *   with every crossing at its edge's midpoint in index space -- points from the inside corners' centroid to the outside corners': a function
+ *   of (tau, case) alone, never of t.  Order: ascending n, then tau, then first / second.  Indices are int32 into the vertex list.
+ *   Normals (optional): g(p) = central difference of f at lattice point p, one-sided at a grid face, each axis divided by its spacing; the
+ *   normal of a vertex is -(g(n) + t (g(n+d) - g(n))), normalised (it points outward); (0,0,0) when its length is zero or not finite.
+ * hav_iso_blocks: the workgroups of a launch, 256 lattice points each; 0 for sizes the entries refuse.
+ * hav_iso_classify: codes [D0 D1 D2] uint32 = crossing mask of the owned edges (bits 0-6) | triangles of the point's cube << 8 | inside bits
+ *   of the cube's corners << 16; block_counts [blocks,2] int32 = (vertices, triangles) per workgroup.  The caller forms the exclusive prefix
+ *   of block_counts over the workgroups (block_offsets [blocks,2] int32), reads the totals V, T and allocates the outputs.
+ * hav_iso_emit: two launches.  The first writes vbase [D0 D1 D2] int32, every point's first vertex index (scan inside the workgroup + its
+ *   offset); the second writes verts [V,3] float32, normals [V,3] float32 (NULL: not computed, nothing else changes) and tris [T,3] int32,
+ *   looking a neighbour's vertex up as vbase[p] + popcount(mask_p & ((1 << e) - 1)).  origin, spacing: three floats each, read on the host.
+ * Every element of [0,V) / [0,T) is written exactly once and nothing beyond.  The same inputs give the same bits on every launch (no
+ * atomics).  NULL pointers (but normals), a D < 2, a non-finite iso: HAV_EINVAL; D0 D1 D2 >= 2^31 or more than 2^31 - 1 workgroups:
+ * HAV_EUNSUP; both before any launch.  No allocation, no synchronisation: capturable. */
+int64_t hav_iso_blocks(int D0, int D1, int D2);
+int hav_iso_classify(uint32_t* codes, int32_t* block_counts, const float* f, int D0, int D1, int D2, float iso, void* stream);
+int hav_iso_emit(float* verts, float* normals, int32_t* tris, int32_t* vbase, const uint32_t* codes, const int32_t* block_offsets,
+                 const float* f, int D0, int D1, int D2, float iso, const float origin[3], const float spacing[3], void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Trilinear x2 up-sampling of a [N,C,D,H,W] float32 volume and its adjoint -- nn.Upsample(scale_factor=2, mode='trilinear',
  * align_corners=False), the first stage of every UpConv3DBlock of the skinning-volume decoder
