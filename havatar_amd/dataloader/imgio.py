@@ -27,6 +27,32 @@ def imwrite_rgb(path, img):
     _pil().fromarray(img, "RGB").save(path, compress_level=3)        # deflate level of cv2.imwrite's default; pixels are lossless either way
 
 
+def imwrite_gray8(path, img):
+    """Write uint8 [H,W] as an 8-bit greyscale PNG."""
+    img = np.ascontiguousarray(img)
+    if img.dtype != np.uint8 or img.ndim != 2:
+        raise ValueError("imwrite_gray8 expects uint8 [H,W]")
+    _pil().fromarray(img, "L").save(path, compress_level=3)
+
+
+def imwrite_gray16(path, hi_lo_u8):
+    """Write uint8 [H,W,2] -- a 16-bit value per pixel, high byte first, which is PNG's own order -- as a 16-bit greyscale PNG."""
+    img = np.ascontiguousarray(hi_lo_u8)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 2:
+        raise ValueError("imwrite_gray16 expects uint8 [H,W,2], high byte first")
+    H, W = img.shape[:2]
+    _pil().frombytes("I;16", (W, H), img.tobytes(), "raw", "I;16B").save(path, compress_level=3)
+
+
+def imread_gray16(path):
+    """uint8 [H,W,2], high byte first, of a 16-bit greyscale PNG (what imwrite_gray16 wrote); any other kind of file is refused."""
+    with _pil().open(path) as im:
+        if im.mode not in ("I;16", "I;16B"):
+            raise ValueError("%s: not a 16-bit greyscale image (mode %s)" % (path, im.mode))
+        v = np.asarray(im).astype(np.uint16)
+    return np.stack([(v >> 8).astype(np.uint8), (v & 255).astype(np.uint8)], -1)
+
+
 def resize_area(img, fx):
     """cv2.resize(img, (0,0), fx=fx, fy=fx, interpolation=cv2.INTER_AREA) for fx = 1/k, k integer: k x k box mean,
     rounded half up for uint8 (OpenCV's saturate_cast), exact for float arrays."""

@@ -21,7 +21,31 @@ Definition of the iso-surface (include/havatar.h carries it too; tests/test_isos
   last two entries are swapped where that makes the right-handed normal (crossings at edge midpoints, index space) point from the inside
   corners' centroid to the outside corners': a table of (tetrahedron, case).  Triangles are ordered by n, tetrahedron, first / second.
   Normal of a vertex: -(g(n) + t (g(n+d) - g(n))) normalised, g = central difference (one-sided at a face) / spacing; (0,0,0) when the
-  length is zero or not finite."""
+  length is zero or not finite.
+
+  gbuffer(rays, depth, acc, H, W, acc_min)     image-space geometry of rendered frames: metric depth, camera-facing normals, headlight shade
+  gbuffer_statement(...)                       the same on ATen, in any dtype; decode_depth16 reads the 16-bit codes back
+
+Contiguous float32 HIP maps take the kernel of csrc/hav_gbuffer.hip (native/gbuffer_ops.py, no fallback in there), every other tensor the
+statement.
+
+Definition of the G-buffer (include/havatar.h carries it too; tests/test_gbuffer_cpu.py restates it in plain loops).
+  rays [B, H W, stride >= 8]: origin 0-2, unit direction 3-5, near 6, far 7 -- the table the march reads; depth [B, H W] = sum w z,
+  acc [B, H W] = sum w; pixel q = (y, x) is row-major.
+  valid(q) = acc > acc_min and isfinite(depth): strict, NaN is invalid.
+  z(q) = min(max(depth / acc, near), far) where valid, else 0 (r < near ? near : r, then > far ? far : that: a NaN quotient stays NaN).
+  p(q) = o + d z.
+  Tangent along an axis (x: neighbours (y, x +- 1); y: (y +- 1, x)).  A side is usable if the neighbour is inside the image and the neighbour
+  and q are both valid.  a+ = |z(q+) - z(q)|, a- = |z(q) - z(q-)|.
+    both usable and max(a+, a-) <= 4 min(a+, a-): central, t = p(q+) - p(q-)  (times 4 is exact, so the choice is);
+    otherwise the usable side with the smaller a, a tie going to +: t = p(q+) - p(q) or p(q) - p(q-);  no usable side: no tangent.
+    The choice keeps silhouettes and depth steps from smearing into the normals next to them.
+  n = tx x ty, negated where n . d(q) > 0, so it faces the camera; normal = n / |n| where both tangents exist and |n| is finite and positive,
+  else (0,0,0).
+  mask: bit 0 = valid, bit 1 = has a normal.  depth16 [..,2] uint8, high byte first: 0 where invalid, else
+  1 + round((z - near) / (far - near) 65534) clamped to [1, 65535].  normal8 = round((n 0.5 + 0.5) 255), (0,0,0) without a normal.
+  shade8 = round(255 max(0, -normal . d)), 255 without a normal.  round: to nearest, ties to even."""
+import collections
 import functools
 
 import numpy as np
@@ -290,6 +314,138 @@ def extract_mesh(trainer, inv_head_T, res=128, iso=DEFAULT_ISO, space="canonical
             T = (trainer.headpose_skin_net.identity_trans.to(verts)[None] if space == "canonical" else inv_head_T[bidx:bidx + 1].to(verts))
             col = density(trainer, verts[None].contiguous(), T, colors=True, bidx=bidx)[1][0]
     return verts, tris, normals, col
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# the G-buffer: depth, normal and shade maps of a rendered frame
+# ------------------------------------------------------------------------------------------------------------------------------------
+GBuffer = collections.namedtuple("GBuffer", "z normal mask depth16 normal8 shade8")
+GBUFFER_U = 2.0 ** -24          # float32's unit round-off: the scale of the conditioning figures in aux
+
+
+def _gb_args(rays, depth, acc, H, W, acc_min):
+    H, W = int(H), int(W)
+    for name, t in (("rays", rays), ("depth", depth), ("acc", acc)):
+        if not torch.is_tensor(t) or not t.is_floating_point():
+            raise ValueError("gbuffer: %s is a floating-point tensor (got %s)" % (name, t.dtype if torch.is_tensor(t) else type(t).__name__))
+    if rays.dim() != 3 or H < 1 or W < 1 or rays.shape[0] < 1 or rays.shape[1] != H * W or rays.shape[2] < 8:
+        raise ValueError("gbuffer: rays is [B, H W, stride >= 8] with H, W >= 1 (got %s for %d x %d)" % (tuple(rays.shape), H, W))
+    B = rays.shape[0]
+    for name, t in (("depth", depth), ("acc", acc)):
+        if t.dim() < 2 or t.shape[0] != B or t.numel() != B * H * W or t.dtype != rays.dtype or t.device != rays.device:
+            raise ValueError("gbuffer: %s holds [B, H W] = [%d, %d] values of the rays' dtype on their device (got %s %s on %s)"
+                             % (name, B, H * W, t.dtype, tuple(t.shape), t.device))
+    acc_min = float(acc_min)
+    if not np.isfinite(acc_min):
+        raise ValueError("gbuffer: acc_min must be finite (got %r)" % acc_min)
+    return B, H, W, acc_min
+
+
+def _gb_shift(t, axis, k):
+    """t at the neighbour q + k along axis (k = +1 / -1), zero / False where that lies outside the image"""
+    out = torch.zeros_like(t)
+    n = t.shape[axis]
+    if k > 0:
+        out.narrow(axis, 0, n - 1).copy_(t.narrow(axis, 1, n - 1))
+    else:
+        out.narrow(axis, 1, n - 1).copy_(t.narrow(axis, 0, n - 1))
+    return out
+
+
+def gbuffer_statement(rays, depth, acc, H, W, acc_min=0.5, choice=None, aux=None):
+    """The definition of the G-buffer (module docstring) on ATen, vectorised, in the inputs' dtype and on their device: GBuffer(z [B,H,W],
+    normal [B,H,W,3], mask [B,H,W] uint8, depth16 [B,H,W,2] uint8, normal8 [B,H,W,3] uint8, shade8 [B,H,W] uint8).  Every operation is rounded
+    on its own and sums run left to right, as in the kernel.
+    choice [B,H,W] uint8: the decisions of another evaluation (bits 0-1 the x tangent's sides, 1 = +, 2 = -, 3 = central, 0 = none; bits 2-3
+    the y tangent's; bit 4 = n was negated) are taken instead of being made -- a float64 evaluation given float32's decisions is the
+    yardstick of the float32 ones.
+    aux: a dict that receives, per pixel, "choice" (this evaluation's decisions, in that coding), "length" = |n| before normalisation,
+    "lx" = |tx|, "ly" = |ty|, "ndot" = n . d before the negation, and "Ex", "Ey": the 2-norm over the components c of
+    3u (M_a + M_b) + u |t_c| with M = |o_c| + |d_c| z at the two pixels the tangent uses and u = 2^-24 -- a bound on float32's error of
+    that tangent."""
+    B, H, W, acc_min = _gb_args(rays, depth, acc, H, W, acc_min)
+    r = rays.reshape(B, H, W, -1)
+    o, d, near, far = r[..., 0:3], r[..., 3:6], r[..., 6], r[..., 7]
+    dep, a = depth.reshape(B, H, W), acc.reshape(B, H, W)
+    zero = torch.zeros((), dtype=rays.dtype, device=rays.device)
+    valid = (a > acc_min) & torch.isfinite(dep)
+    q = dep / a
+    q = torch.where(q < near, near, q)
+    q = torch.where(q > far, far, q)
+    z = torch.where(valid, q, zero)
+    p = o + d * z[..., None]
+    M = o.abs() + d.abs() * z[..., None]
+    tangents, sides, errs = [], [], []
+    for axis, shift in ((2, 0), (1, 2)):          # x: neighbours (y, x +- 1); y: (y +- 1, x)
+        if choice is None:
+            vp, vm = valid & _gb_shift(valid, axis, 1), valid & _gb_shift(valid, axis, -1)
+            ap, am = (_gb_shift(z, axis, 1) - z).abs(), (z - _gb_shift(z, axis, -1)).abs()
+            gt = ap > am
+            mx, mn = torch.where(gt, ap, am), torch.where(gt, am, ap)
+            central = vp & vm & (mx <= 4.0 * mn)
+            plus = ~central & vp & (~vm | (ap <= am))
+            minus = ~central & ~plus & vm
+            side = central.to(torch.uint8) * 3 + plus.to(torch.uint8) + minus.to(torch.uint8) * 2
+        else:
+            side = (choice.reshape(B, H, W).to(device=rays.device, dtype=torch.uint8) >> shift) & 3
+        up, um = ((side & 1) != 0)[..., None], ((side & 2) != 0)[..., None]
+        t = torch.where(up, _gb_shift(p, axis, 1), p) - torch.where(um, _gb_shift(p, axis, -1), p)
+        e = 3.0 * GBUFFER_U * (torch.where(up, _gb_shift(M, axis, 1), M) + torch.where(um, _gb_shift(M, axis, -1), M)) + GBUFFER_U * t.abs()
+        tangents.append(t)
+        sides.append(side)
+        errs.append((e[..., 0] * e[..., 0] + e[..., 1] * e[..., 1] + e[..., 2] * e[..., 2]).sqrt())
+    (tx, ty), (sx, sy) = tangents, sides
+    n = torch.stack([tx[..., 1] * ty[..., 2] - tx[..., 2] * ty[..., 1], tx[..., 2] * ty[..., 0] - tx[..., 0] * ty[..., 2],
+                     tx[..., 0] * ty[..., 1] - tx[..., 1] * ty[..., 0]], -1)
+    ndot = n[..., 0] * d[..., 0] + n[..., 1] * d[..., 1] + n[..., 2] * d[..., 2]
+    flip = ndot > 0 if choice is None else (choice.reshape(B, H, W).to(device=rays.device, dtype=torch.uint8) & 16) != 0
+    n = torch.where(flip[..., None], -n, n)
+    length = (n[..., 0] * n[..., 0] + n[..., 1] * n[..., 1] + n[..., 2] * n[..., 2]).sqrt()
+    has = (sx != 0) & (sy != 0) & torch.isfinite(length) & (length > 0)
+    normal = torch.where(has[..., None], n / length[..., None], zero)
+    if aux is not None:
+        norm3 = lambda t: (t[..., 0] * t[..., 0] + t[..., 1] * t[..., 1] + t[..., 2] * t[..., 2]).sqrt()
+        aux.update(choice=sx | (sy << 2) | (flip.to(torch.uint8) << 4), length=length, lx=norm3(tx), ly=norm3(ty), Ex=errs[0], Ey=errs[1],
+                   ndot=ndot)
+    # the codes
+    mask = valid.to(torch.uint8) | (has.to(torch.uint8) << 1)
+    dc = torch.round((z - near) / (far - near) * 65534.0)
+    code = torch.where(dc >= 65534.0, torch.full_like(dc, 65535.0), torch.where(dc >= 0, dc + 1.0, torch.ones_like(dc)))
+    code = torch.where(valid, code, zero).to(torch.int32)
+    depth16 = torch.stack([code >> 8, code & 255], -1).to(torch.uint8)
+    normal8 = torch.where(has[..., None], torch.round((normal * 0.5 + 0.5) * 255.0), zero).to(torch.uint8)
+    lam = -(normal[..., 0] * d[..., 0] + normal[..., 1] * d[..., 1] + normal[..., 2] * d[..., 2])
+    lam = torch.where(lam > 0, lam, zero)
+    sc = torch.round(255.0 * lam)
+    shade8 = torch.where(has, torch.where(sc >= 255.0, torch.full_like(sc, 255.0), sc), torch.full_like(sc, 255.0)).to(torch.uint8)
+    return GBuffer(z, normal, mask, depth16, normal8, shade8)
+
+
+def gbuffer(rays, depth, acc, H, W, acc_min=0.5):
+    """Depth, normal and shade maps of B rendered frames from what the ray march read and wrote: rays [B, H W, stride >= 8] (origin, unit
+    direction, near, far), depth [B, H W] = sum w z and acc [B, H W] = sum w (Trainer.nerf_forward's depth_fine and acc_fine).  Returns
+    GBuffer(z, normal, mask, depth16, normal8, shade8) -- the module docstring has the definition; depth16 / normal8 / shade8 are what
+    imgio.imwrite_gray16 / imwrite_rgb / imwrite_gray8 write.
+
+    Contiguous float32 HIP tensors take the kernel (native/gbuffer_ops.py): one launch for all frames on the current stream, nothing read
+    back.  Any other tensor takes the ATen statement."""
+    B, H, W, acc_min = _gb_args(rays, depth, acc, H, W, acc_min)
+    with torch.no_grad():
+        if rays.is_cuda and rays.dtype == torch.float32 and rays.is_contiguous() and depth.is_contiguous() and acc.is_contiguous():
+            from .native import gbuffer_ops
+            out = gbuffer_ops.gbuffer(rays, depth, acc, H, W, acc_min, outputs=GBuffer._fields)
+            return GBuffer(*[out[k] for k in GBuffer._fields])
+        return gbuffer_statement(rays, depth, acc, H, W, acc_min)
+
+
+DEPTH16_CODE = "0 = no surface (acc <= acc_min or depth not finite); else z = near + (code - 1) / 65534 * (far - near)"
+
+
+def decode_depth16(depth16, near, far):
+    """float64 z of the 16-bit codes ([...,2] uint8, high byte first), NaN where the code is 0"""
+    c = depth16[..., 0].to(torch.float64) * 256.0 + depth16[..., 1].to(torch.float64)
+    z = near + (c - 1.0) / 65534.0 * (far - near)
+    return torch.where(c > 0, z, torch.full_like(z, float("nan")))
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------

@@ -60,6 +60,11 @@ def parse_args(argv=None):
     p.add_argument("--mesh-iso", type=float, default=None, help="--mesh: density level of the surface (default: geometry.DEFAULT_ISO).")
     p.add_argument("--mesh-space", choices=("canonical", "posed"), default="canonical", help="--mesh: the canonical box (pose-free) or the "
                    "frame's posed box.")
+    p.add_argument("--gbuffer", action="store_true", help="Write every frame's geometry as images at the render size (havatar_amd.geometry."
+                   "gbuffer): <savedir>/depth/<fidx>_<view>.png (16-bit), normal/ (RGB8), shade/ (grey8), and <savedir>/gbuffer.json with "
+                   "near, far and the codes' definition.")
+    p.add_argument("--gbuffer-acc-min", type=float, default=0.5, help="--gbuffer: a pixel shows a surface where the accumulated opacity "
+                   "exceeds this.")
     return p.parse_args(argv)
 
 
@@ -158,10 +163,39 @@ def frame_mesh(nerf_render, inv_head_T, bidx, args):
     return [t.cpu().numpy() for t in mesh]
 
 
+def frame_gbuffer(inp, outs, n, args):
+    """--gbuffer: the maps of the n frames just rendered, from the ray table the march read and the depth and accumulation it returned, on the
+    current stream after the frame; (depth16 [n,S,S,2], normal8 [n,S,S,3], shade8 [n,S,S]) as host arrays for the PNG writers"""
+    from .. import geometry
+    S = outs[0].shape[-1]
+    gb = geometry.gbuffer(inp["ray_batch"], outs[3].reshape(n, S * S), outs[1].reshape(n, S * S), S, S, args.gbuffer_acc_min)
+    return [t.cpu().numpy() for t in (gb.depth16, gb.normal8, gb.shade8)]
+
+
+def write_gbuffer_table(savedir, rank, world, args, near, far, size, files):
+    from ..geometry import DEPTH16_CODE
+    path = os.path.join(savedir, "gbuffer.json" if world == 1 else "gbuffer_rank%dof%d.json" % (rank, world))
+    with open(path, "w") as f:
+        json.dump({"near": near, "far": far, "acc_min": args.gbuffer_acc_min, "size": size,
+                   "depth": "16-bit grey, metres along the ray: " + DEPTH16_CODE,
+                   "normal": "RGB8 = round((n * 0.5 + 0.5) * 255), n the unit normal facing the camera in the frame's posed world space; "
+                             "(0,0,0) = no normal",
+                   "shade": "grey8 = round(255 * max(0, -n . d)), d the pixel's ray direction; 255 = no normal",
+                   "files": files}, f, indent=1)
+    return path
+
+
 def main(argv=None, device=None, style=None):
-    """Returns the PNG paths; main.mesh_written lists the PLY paths of the last call (empty without --mesh)."""
+    """Returns the PNG paths; main.mesh_written lists the PLY paths of the last call (empty without --mesh), main.gbuffer_written the
+    depth / normal / shade PNG paths (empty without --gbuffer)."""
     args = parse_args(argv)
     main.mesh_written = []
+    main.gbuffer_written = []
+    if args.gbuffer:
+        if not np.isfinite(args.gbuffer_acc_min):
+            raise RuntimeError("--gbuffer-acc-min %r: the threshold must be finite" % args.gbuffer_acc_min)
+        for sub in ("depth", "normal", "shade"):
+            os.makedirs(os.path.join(args.savedir, sub), exist_ok=True)
     os.makedirs(os.path.join(args.savedir, "rgb"), exist_ok=True)
     if args.mesh:
         if args.mesh_res < 2:
@@ -214,6 +248,7 @@ def main(argv=None, device=None, style=None):
     graphed, graphed2, written = {}, {}, []            # hipGraphs per batch size (the last batch of a split may be ragged)
     writers = ThreadPoolExecutor(max_workers=switches.integer("HAVATAR_PNG_THREADS"))    # PNG deflate off the critical path (a 1024^2 frame is ~70 ms of zlib on one core)
     pending, ring, in_flight = [], [None, None], None
+    gb_range = None
     t_first = t_loop = None
     with torch.no_grad():
         for idx, val_batch in frames:
@@ -223,6 +258,8 @@ def main(argv=None, device=None, style=None):
                 t_loop = time.perf_counter()             # steady state starts after the first frame (solver search, graph capture)
             n = int(val_batch["fidx"].shape[0])
             inp = frame_inputs(idx, val_batch, device, size=val_loader.dataset.img_h, cache=ray_cache)
+            if args.gbuffer:
+                inp["return_depth"] = True          # not a tensor: part of the captured callable's fixed arguments below
             styles = [style if n == 1 else style.expand(n, -1)]
             gt_imgs = val_batch["gt_img"].to(device, non_blocking=True) if scores is not None else None
             if use_graph:
@@ -230,14 +267,20 @@ def main(argv=None, device=None, style=None):
                 if n not in graphed:
                     fixed = {k_: v for k_, v in inp.items() if k_ not in tens}
                     graphed[n] = GraphedForward(lambda fixed=fixed, **kw: nerf_render(**kw, **fixed), tens)
-                render, _, _ = graphed[n](**tens)
+                outs = graphed[n](**tens)
+                render = outs[0]
                 cond = {"condition_img": render[:, 3:].contiguous()}
                 if n not in graphed2:
                     graphed2[n] = GraphedForward(lambda condition_img, styles=styles: img_trans(styles=styles, condition_img=condition_img), cond)
                 gen_imgs = graphed2[n](**cond)
             else:
-                render, _, _ = nerf_render(**inp)
+                outs = nerf_render(**inp)
+                render = outs[0]
                 gen_imgs = img_trans(styles=styles, condition_img=render[:, 3:])
+            if args.gbuffer:
+                gb_maps = frame_gbuffer(inp, outs, n, args)
+                if gb_range is None:
+                    gb_range = [float(v) for v in inp["ray_batch"][0, 0, 6:8].cpu()]
             for b in range(n):
                 gen_img = gen_imgs[b:b + 1]
                 name, k = str(int(val_batch["fidx"][b])), int(val_batch["vidx"][0][b])          # ("vidx" is a one-element list per item: collated to [tensor[n]])
@@ -247,6 +290,10 @@ def main(argv=None, device=None, style=None):
                     from ..geometry import write_ply
                     main.mesh_written.append(os.path.join(args.savedir, "mesh", f"{name}_{k:02d}.ply"))
                     pending.append(writers.submit(write_ply, main.mesh_written[-1], *frame_mesh(nerf_render, inp["inv_head_T"], b, args)))
+                if args.gbuffer:
+                    for sub, fn, arr in zip(("depth", "normal", "shade"), (imgio.imwrite_gray16, imgio.imwrite_rgb, imgio.imwrite_gray8), gb_maps):
+                        main.gbuffer_written.append(os.path.join(args.savedir, sub, f"{name}_{k:02d}.png"))
+                        pending.append(writers.submit(fn, main.gbuffer_written[-1], arr[b]))
                 if device.type != "cuda":
                     arr = to_png_array(gen_img)
                     if scores is not None:
@@ -287,6 +334,9 @@ def main(argv=None, device=None, style=None):
                                                             nerf_render.render_size, nerf_render.render_size, gen_img.shape[-1], gen_img.shape[-2]))
     if scores is not None:
         print("[metrics] %s" % scores.write(args.savedir, rank, world))
+    if args.gbuffer and gb_range is not None:
+        print("[gbuffer] %s" % write_gbuffer_table(args.savedir, rank, world, args, gb_range[0], gb_range[1], nerf_render.render_size,
+                                                   [os.path.relpath(p, args.savedir) for p in main.gbuffer_written]))
     print("Done!")
     return written
 

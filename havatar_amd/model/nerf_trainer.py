@@ -119,7 +119,7 @@ class Trainer(torch.nn.Module):
             # batched inference (B frames per call: frames.py / bench.py --workload cfg3 --batch): the one validation code serves every frame
             # of the batch.  (The reference only ever calls this with B = 1 -- its cat([latent, cond_c]) does not broadcast.)
             latent_code = latent_code.expand(B, -1)
-        rgb_coarse, _, acc_coarse, weights, rgb_fine, _, acc_fine = self.nerf_forward(
+        rgb_coarse, depth_coarse, acc_coarse, weights, rgb_fine, _, acc_fine = self.nerf_forward(
             ray_batch=ray_batch, background_prior=background_prior, latent_code=latent_code, inv_head_T=data["inv_head_T"],
             front_render_cond=data["front_render_cond"], left_render_cond=data["left_render_cond"],
             right_render_cond=data["right_render_cond"], mode=data["mode"], _fine_maps_only=bool(data["render_full_img"]))
@@ -128,6 +128,10 @@ class Trainer(torch.nn.Module):
             mask = acc_fine if acc_fine is not None else acc_coarse
             render = render.reshape(B, self.render_size, self.render_size, -1).permute(0, 3, 1, 2)
             mask = mask.reshape(B, self.render_size, self.render_size, -1).permute(0, 3, 1, 2)
+            if data.get("return_depth", False):
+                # the march's expected depth sum w z of the pass the image comes from (havatar_amd.geometry.gbuffer turns it into maps)
+                depth = _ if rgb_fine is not None else depth_coarse
+                return render, mask, latent_code_loss, depth.reshape(B, 1, self.render_size, self.render_size)
             return render, mask, latent_code_loss
         return rgb_coarse, _, acc_coarse, weights, rgb_fine, _, acc_fine, latent_code_loss
 

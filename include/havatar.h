@@ -541,6 +541,34 @@ int hav_iso_classify(uint32_t* codes, int32_t* block_counts, const float* f, int
 int hav_iso_emit(float* verts, float* normals, int32_t* tris, int32_t* vbase, const uint32_t* codes, const int32_t* block_offsets,
                  const float* f, int D0, int D1, int D2, float iso, const float origin[3], const float spacing[3], void* stream);
 
+/* G-buffer of a rendered frame: metric depth, camera-facing normals and a headlight shade from the maps of the ray march
+ * (csrc/hav_gbuffer.hip; added within ABI 8: additive) -- the kernel behind havatar_amd.geometry.gbuffer.  No reference counterpart.
+ *   Inputs, float32 and contiguous: rays [B, H W, stride >= 8] (origin 0-2, unit direction 3-5, near 6, far 7: the table hav_render_rays
+ *   reads), depth [B, H W] = sum w z, acc [B, H W] = sum w.  Pixel q = (y, x) is row-major.
+ *   valid(q) = acc > acc_min and isfinite(depth) (strict; NaN is invalid).
+ *   z(q) = min(max(depth / acc, near), far) where valid, else 0; the division is float32, correctly rounded.  (With r = depth / acc the
+ *   clamp is r < near ? near : r, then > far ? far : that: a NaN r stays NaN.)
+ *   p(q) = o + d z, the product rounded before the sum.
+ *   Tangent along an axis (x: neighbours (y, x +- 1); y: (y +- 1, x)): a side is usable if the neighbour is inside the image and the
+ *   neighbour and q are both valid.  a+ = |z(q+) - z(q)|, a- = |z(q) - z(q-)|, float32.
+ *     both usable and max(a+, a-) <= 4 min(a+, a-): central, t = p(q+) - p(q-) (the factor 4 is exact, so is the choice);
+ *     otherwise the usable side with the smaller a, a tie going to +: t = p(q+) - p(q) or p(q) - p(q-);  no usable side: no tangent.
+ *   n = tx x ty, negated where n . d(q) > 0 (it faces the camera); normal = n / |n| where both tangents exist and |n| is finite and
+ *   positive, else (0,0,0).  Every operation is rounded on its own (no fused multiply-add), sums run left to right.
+ * Outputs, each optional (NULL: not written), at least one given:
+ *   z [B,H,W] float32;  normal [B,H,W,3] float32, in the frame's posed world space;  mask [B,H,W] uint8: bit 0 = valid, bit 1 = has a normal;
+ *   depth16 [B,H,W,2] uint8, high byte first: 0 where invalid, else 1 + round((z - near) / (far - near) 65534) clamped to [1, 65535];
+ *   normal8 [B,H,W,3] uint8 = round((n 0.5 + 0.5) 255), (0,0,0) without a normal;
+ *   shade8 [B,H,W] uint8 = round(255 max(0, -normal . d)), 255 without a normal;  round = to nearest, ties to even;
+ *   choice [B,H,W] uint8, the decisions: bits 0-1 the x tangent's sides (1 = +, 2 = -, 3 = central, 0 = none), bits 2-3 the y tangent's,
+ *   bit 4 = n was negated.
+ * One launch for all B frames, a 256-thread workgroup per hav_gbuffer_tile(0) x hav_gbuffer_tile(1) = 4 x 64 pixel tile; every output
+ * element is written exactly once and nothing beyond; no atomics: the same inputs give the same bits.  NULL inputs, no output, B / H / W < 1,
+ * stride < 8, a non-finite acc_min, B H W stride >= 2^31: HAV_EINVAL, before any launch.  No allocation, no synchronisation: capturable. */
+int hav_gbuffer_tile(int axis);
+int hav_gbuffer_f32(float* z, float* normal, uint8_t* mask, uint8_t* depth16, uint8_t* normal8, uint8_t* shade8, uint8_t* choice,
+                    const float* rays, const float* depth, const float* acc, int B, int H, int W, int stride, float acc_min, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Trilinear x2 up-sampling of a [N,C,D,H,W] float32 volume and its adjoint -- nn.Upsample(scale_factor=2, mode='trilinear',
  * align_corners=False), the first stage of every UpConv3DBlock of the skinning-volume decoder
