@@ -135,7 +135,9 @@ def lib():
                        ("hav_iso_classify", [vp] * 3 + [i32] * 3 + [f32, vp]),
                        ("hav_iso_emit", [vp] * 7 + [i32] * 3 + [f32, C.POINTER(f32), C.POINTER(f32), vp]),
                        ("hav_gbuffer_tile", [i32]),
-                       ("hav_gbuffer_f32", [vp] * 10 + [i32] * 4 + [f32, vp])):
+                       ("hav_gbuffer_f32", [vp] * 10 + [i32] * 4 + [f32, vp]),
+                       ("hav_raster_param", [i32]),
+                       ("hav_raster_ortho_f32", [vp] * 11 + [i32] * 6 + [C.POINTER(f32), vp])):
         try:
             fn = getattr(L, name)
         except AttributeError:

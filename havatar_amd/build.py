@@ -15,7 +15,7 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libhavatar_hip.so")
 SOURCES = ["hav_ops.hip", "hav_render.hip", "hav_train.hip", "hav_mlp_train.hip", "hav_conv.hip", "hav_conv3d.hip", "hav_decoder.hip",
            "hav_composite_long.hip", "hav_stage2.hip", "hav_s2_loss.hip", "hav_lpips.hip", "hav_metrics.hip", "hav_ssim_loss.hip",
-           "hav_isosurface.hip", "hav_gbuffer.hip"]
+           "hav_isosurface.hip", "hav_gbuffer.hip", "hav_raster.hip"]
 HEADERS = ["hav_common.h", os.path.join("..", "..", "include", "havatar.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-variable"]
 BUILD_INFO = os.path.join(LIBDIR, "BUILD_INFO.json")

@@ -33,6 +33,8 @@ class SplitFileDataset(Dataset):
     {"img_res", "mutiview_intr_ls" [[fx,fy,cx/W,cy/H],..], "bg_path"?, "frames": [{"fidx", "inst_dir", "head_transformation" [4,4],
       "mutiview_info_ls": [{"view_name", "transform_matrix", "transform_matrix_ori", "cam_K"?, "file_path", "mask_path"}]}]}"""
     skip_view = None
+    cond_mesh = False                                # read <inst_dir>/cond_mesh.npz (cond_vs, cond_color) instead of the six condition PNGs
+    cond_mesh_verts = None                           # mesh mode: refuse a frame whose vertex count differs from this
 
     def __init__(self, split_file, mode, options, down_sample=1.0, white_bg=True):
         super().__init__()
@@ -118,7 +120,13 @@ class SplitFileDataset(Dataset):
     def add_conditions(self, data_dict, frame_dict):
         """3 orthographic 3DMM renders + the head pose (dataloader.py:205-220)."""
         res = self.options.dataset.cond_render_res
-        for v in COND_VIEWS:
+        if self.cond_mesh:
+            # mesh mode: the frame's tracked vertices and colours travel instead of the six PNGs; the consumer rasterises them
+            # (havatar_amd.conditions.render_conditions).  cond_mesh_verts: the vertex count of the topology the consumer holds, if known.
+            from ..conditions import read_cond_mesh
+            vs, color = read_cond_mesh(frame_dict["inst_dir"], self.cond_mesh_verts)
+            data_dict["cond_vs"], data_dict["cond_color"] = torch.from_numpy(vs), torch.from_numpy(color)
+        for v in () if self.cond_mesh else COND_VIEWS:
             data_dict[v + "_render_cond"] = make_render_cond_(
                 os.path.join(frame_dict["inst_dir"], "ortho_%s_normal_256_baseGama.png" % v),
                 os.path.join(frame_dict["inst_dir"], "ortho_%s_render_256_baseGama.png" % v), res)

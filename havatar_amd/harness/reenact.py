@@ -65,6 +65,11 @@ def parse_args(argv=None):
                    "near, far and the codes' definition.")
     p.add_argument("--gbuffer-acc-min", type=float, default=0.5, help="--gbuffer: a pixel shows a surface where the accumulated opacity "
                    "exceeds this.")
+    p.add_argument("--cond-mesh", type=str, default="", metavar="TRI.npy", help="Mesh mode: drive the avatar with every frame's tracked mesh "
+                   "(<inst_dir>/cond_mesh.npz: vs [V,3], color [V,3]) and this integer [F,3] topology; the three condition renders are "
+                   "rasterised per frame (havatar_amd.conditions.render_conditions) instead of being read from the six PNGs.")
+    p.add_argument("--cond-cam-dist", type=float, default=10.0, help="--cond-mesh: distance of the orthographic camera.")
+    p.add_argument("--cond-write", action="store_true", help="--cond-mesh: also write the six condition PNGs into each frame's inst_dir.")
     return p.parse_args(argv)
 
 
@@ -81,9 +86,18 @@ def build_models(cfg, checkpoint, device):
     return nerf_render.eval(), img_trans.eval()
 
 
-def frame_inputs(idx, batch, device, size=None, cache=None):
+def frame_conditions(batch, device, mesh):
+    """--cond-mesh: the frame's Conditions from its tracked vertices, on the frame's device.  mesh = (Topology, cam_dist)"""
+    from .. import conditions
+    topo, cam_dist = mesh
+    return conditions.render_conditions(batch["cond_vs"].to(device, non_blocking=True), batch["cond_color"].to(device, non_blocking=True), topo,
+                                        cam_dist=cam_dist)
+
+
+def frame_inputs(idx, batch, device, size=None, cache=None, mesh=None):
     """The dict the reference builds per frame (:151-159).  With a `camera` record in the batch (device-ray mode) the ray table is
-    generated on the device (hav_gen_rays) and the white background prior is a cached constant."""
+    generated on the device (hav_gen_rays) and the white background prior is a cached constant.  With `mesh` (--cond-mesh) the three
+    condition tensors are rasterised from the frame's tracked mesh, eagerly, and the Conditions is left in cache["conditions"]."""
     if "camera" in batch:
         from ..render import gen_rays
         n = batch["camera"].shape[0]
@@ -98,6 +112,17 @@ def frame_inputs(idx, batch, device, size=None, cache=None):
     else:
         rays = batch["mv_rays"]
         ray_batch, bg = rays[..., :-3].to(device), rays[..., -3:].to(device)
+    if mesh is not None:
+        out = frame_conditions(batch, device, mesh)
+        if cache is not None:
+            cache["conditions"] = out
+        # the kernel wrote [n,3,7,H,W]; nothing crosses PCIe but the vertices.  The PNG route hands over channels-last views of [n,H,W,7]:
+        # the same strides here (one device copy of 0.46 MB per view), so that both routes hand the encoders identical tensors, strides
+        # included, and a convolution that picks its kernel by memory format picks the same one
+        view = lambda k: out.cond[:, k].contiguous(memory_format=torch.channels_last)
+        return {"mode": "validation", "fidx": idx, "render_full_img": True, "ray_batch": ray_batch, "background_prior": bg,
+                "front_render_cond": view(0), "left_render_cond": view(1), "right_render_cond": view(2),
+                "inv_head_T": batch["inv_head_T"].to(device)}
     return {"mode": "validation", "fidx": idx, "render_full_img": True,
             "ray_batch": ray_batch, "background_prior": bg,
             # channels-last host images go over PCIe as they are (contiguous, pinned by the loader); the NHWC -> NCHW permutation
@@ -187,10 +212,15 @@ def write_gbuffer_table(savedir, rank, world, args, near, far, size, files):
 
 def main(argv=None, device=None, style=None):
     """Returns the PNG paths; main.mesh_written lists the PLY paths of the last call (empty without --mesh), main.gbuffer_written the
-    depth / normal / shade PNG paths (empty without --gbuffer)."""
+    depth / normal / shade PNG paths (empty without --gbuffer), main.cond_written the condition PNG paths (empty without --cond-write)."""
     args = parse_args(argv)
     main.mesh_written = []
     main.gbuffer_written = []
+    main.cond_written = []
+    if args.cond_write and not args.cond_mesh:
+        raise RuntimeError("--cond-write writes the condition PNGs rendered from the tracked mesh: it needs --cond-mesh TRI.npy")
+    if args.cond_mesh and not np.isfinite(args.cond_cam_dist):
+        raise RuntimeError("--cond-cam-dist %r: the distance must be finite" % args.cond_cam_dist)
     if args.gbuffer:
         if not np.isfinite(args.gbuffer_acc_min):
             raise RuntimeError("--gbuffer-acc-min %r: the threshold must be finite" % args.gbuffer_acc_min)
@@ -230,6 +260,13 @@ def main(argv=None, device=None, style=None):
     # HIP: the loader ships 18 camera floats per frame and the ray table is built on the device
     val_loader.dataset.device_rays = device.type == "cuda" and switches.on("HAVATAR_DEVICE_RAYS")
     ray_cache = {}
+    cond_mesh = None
+    if args.cond_mesh:
+        from .. import conditions
+        first = val_loader.dataset.frames[0]["inst_dir"] if len(val_loader.dataset) else None
+        V = conditions.read_cond_mesh(first)[0].shape[0] if first is not None else None
+        cond_mesh = (conditions.Topology.load(args.cond_mesh, V), args.cond_cam_dist)
+        val_loader.dataset.cond_mesh, val_loader.dataset.cond_mesh_verts = True, cond_mesh[0].V
     scores = None
     if args.metrics:
         val_loader.dataset.with_gt = True
@@ -257,7 +294,9 @@ def main(argv=None, device=None, style=None):
             elif t_loop is None:
                 t_loop = time.perf_counter()             # steady state starts after the first frame (solver search, graph capture)
             n = int(val_batch["fidx"].shape[0])
-            inp = frame_inputs(idx, val_batch, device, size=val_loader.dataset.img_h, cache=ray_cache)
+            inp = frame_inputs(idx, val_batch, device, size=val_loader.dataset.img_h, cache=ray_cache, mesh=cond_mesh)
+            if args.cond_write:
+                cond_maps = [t.cpu().numpy() for t in (ray_cache["conditions"].render8, ray_cache["conditions"].normal8)]
             if args.gbuffer:
                 inp["return_depth"] = True          # not a tensor: part of the captured callable's fixed arguments below
             styles = [style if n == 1 else style.expand(n, -1)]
@@ -286,6 +325,13 @@ def main(argv=None, device=None, style=None):
                 name, k = str(int(val_batch["fidx"][b])), int(val_batch["vidx"][0][b])          # ("vidx" is a one-element list per item: collated to [tensor[n]])
                 path = os.path.join(args.savedir, "rgb", f"{name}_{k:02d}.png")
                 written.append(path)
+                if args.cond_write:
+                    from ..conditions import VIEWS, png_names
+                    inst = val_loader.dataset.frames[int(idx[b])]["inst_dir"]
+                    for v, view in enumerate(VIEWS):
+                        for fname, arr in zip(png_names(view), cond_maps):
+                            main.cond_written.append(os.path.join(inst, fname))
+                            pending.append(writers.submit(imgio.imwrite_rgb, main.cond_written[-1], np.ascontiguousarray(arr[b, v])))
                 if args.mesh:
                     from ..geometry import write_ply
                     main.mesh_written.append(os.path.join(args.savedir, "mesh", f"{name}_{k:02d}.ply"))

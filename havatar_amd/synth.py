@@ -261,23 +261,60 @@ def cond_images(B=1, res=256, seed=60):
     return out
 
 
-def write_dataset(root, n_frames=2, img_res=128, focal=1.7, cam_dist=5.0, seed=60, views=("0",), photos=True):
+def head_mesh(k=0, n_lat=12, n_lon=16):
+    """A small tracked-head stand-in in the fitted model's space: a UV sphere with a nose towards -z (the front view's camera looks along +z), turned and scaled a little with the
+    frame number k.  (vs [V,3] float32, color [V,3] float32 in 30...250, tris [F,3] int32); the topology does not depend on k."""
+    th = np.linspace(0.0, math.pi, n_lat + 1)[1:-1]
+    ph = np.arange(n_lon) * (2.0 * math.pi / n_lon)
+    ring = np.stack([np.outer(np.sin(th), np.sin(ph)), np.outer(np.cos(th), np.ones(n_lon)), np.outer(np.sin(th), np.cos(ph))], -1).reshape(-1, 3)
+    unit = np.concatenate([[[0.0, 1.0, 0.0]], ring, [[0.0, -1.0, 0.0]]], 0)
+    nose = np.exp(-((unit[:, 0] / 0.35) ** 2 + ((unit[:, 1] + 0.1) / 0.35) ** 2)) * (unit[:, 2] < 0)
+    rad = (0.95 + 0.01 * k) * (1.0 + 0.25 * nose)
+    yaw = 0.15 * math.sin(1.3 * k)
+    R = np.array([[math.cos(yaw), 0.0, math.sin(yaw)], [0.0, 1.0, 0.0], [-math.sin(yaw), 0.0, math.cos(yaw)]])
+    vs = (unit * rad[:, None] * np.array([0.9, 1.15, 1.0])) @ R.T + np.array([0.03, -0.12, -0.15])
+    color = np.stack([140.0 + 100.0 * unit[:, 0], 130.0 + 90.0 * unit[:, 1], 120.0 + 80.0 * unit[:, 2]], -1) + 10.0 * nose[:, None]
+    last = 1 + (n_lat - 1) * n_lon
+    tris = []
+    for j in range(n_lon):
+        jn = (j + 1) % n_lon
+        tris.append((0, 1 + j, 1 + jn))
+        tris.append((last, 1 + (n_lat - 2) * n_lon + jn, 1 + (n_lat - 2) * n_lon + j))
+        for i in range(n_lat - 2):
+            a, b, c, d = 1 + i * n_lon + j, 1 + i * n_lon + jn, 1 + (i + 1) * n_lon + j, 1 + (i + 1) * n_lon + jn
+            tris += [(a, c, d), (a, d, b)]
+    return vs.astype(np.float32), np.clip(color, 30.0, 250.0).astype(np.float32), np.asarray(tris, np.int32)
+
+
+def write_dataset(root, n_frames=2, img_res=128, focal=1.7, cam_dist=5.0, seed=60, views=("0",), photos=True, cond_mesh=False):
     """A tiny synthetic dataset in the reference's on-disk layout (split file `sv_v31_all.json` + PNGs, see
     havatar_amd/dataloader/_base.py) for the harness tests and demos: pinhole camera of SURVEY 8(d), per-frame head pose
     `frame_pose(k)`, 256^2 3DMM condition renders from `cond_images`, a shaded-disc photograph and its mask per view
-    (`photos=False` skips those two: test-mode readers never open them).  Returns the split-file path."""
+    (`photos=False` skips those two: test-mode readers never open them).  Returns the split-file path.
+    cond_mesh=True: every frame also gets `cond_mesh.npz` (vs, color of `head_mesh(k)`), `tri.npy` lies next to the split file, and the six
+    condition PNGs are that mesh rendered by `conditions.conditions_statement`, so the PNGs and the mesh describe the same frame."""
     import json
     import os
 
     from .dataloader import imgio
     os.makedirs(root, exist_ok=True)
+    if cond_mesh:
+        import torch
+
+        from . import conditions
+        np.save(os.path.join(root, "tri.npy"), head_mesh(0)[2])
     c2w = [[1.0, 0.0, 0.0, 0.0], [0.0, -1.0, 0.0, 0.0], [0.0, 0.0, -1.0, cam_dist], [0.0, 0.0, 0.0, 1.0]]
     yy, xx = np.meshgrid(np.arange(img_res), np.arange(img_res), indexing="ij")
     frames = []
     for k in range(n_frames):
         inst = os.path.join(root, "frame_%04d" % k)
         os.makedirs(inst, exist_ok=True)
-        for name, img in zip(("front", "left", "right"), cond_images(1, 256, seed + 10 * k)):
+        if cond_mesh:
+            vs, color, tris = head_mesh(k)
+            np.savez(os.path.join(inst, conditions.MESH_FILE), vs=vs, color=color)
+            conditions.write_condition_pngs(inst, conditions.conditions_statement(torch.from_numpy(vs)[None], torch.from_numpy(color)[None],
+                                                                                  torch.from_numpy(tris)), 0)
+        for name, img in () if cond_mesh else zip(("front", "left", "right"), cond_images(1, 256, seed + 10 * k)):
             m = img[0, 6][..., None]
             render = np.floor(img[0, 0:3].transpose(1, 2, 0) * m * 255 + 0.5).astype(np.uint8)
             normal = np.floor((0.02 + 0.98 * img[0, 3:6].transpose(1, 2, 0)) * m * 255 + 0.5).astype(np.uint8)

@@ -569,6 +569,36 @@ int hav_gbuffer_tile(int axis);
 int hav_gbuffer_f32(float* z, float* normal, uint8_t* mask, uint8_t* depth16, uint8_t* normal8, uint8_t* shade8, uint8_t* choice,
                     const float* rays, const float* depth, const float* acc, int B, int H, int W, int stride, float acc_min, void* stream);
 
+/* Condition images from a tracked mesh: three orthographic, z-buffered renders per frame with ambient vertex colours, the depth-to-normal
+ * pass and the 7-channel condition planes (csrc/hav_raster.hip; added within ABI 8: additive) -- the kernels behind
+ * havatar_amd.conditions.render_conditions.
+ *   Inputs, contiguous: verts [B,V,3] float32; colors [B,V,3] (colors_batched != 0) or [V,3] float32, 0...255; tris [F,3] int32;
+ *   view34, 34 floats read on the host: scale[3], trans[3], rot[3][3][3] (view, row, column), cam_dist.
+ *   Screen: w = v scale + trans; in view k, r_c = (w.x rot[k][0][c] + w.y rot[k][1][c]) + w.z rot[k][2][c]; vertex = (r.x, r.y, r.z + cam_dist).
+ *   Pixel (i, j) samples X = (2 j + 1) / W - 1, Y = (2 i + 1) / H - 1.
+ *   Triangle (a, b, c): area = (bx-ax)(cy-ay) - (by-ay)(cx-ax); it takes no part when area == 0, a coordinate is not finite or an index lies
+ *   outside [0, V).  w0 = (bx-X)(cy-Y) - (by-Y)(cx-X), w1 = (cx-X)(ay-Y) - (cy-Y)(ax-X), w2 = (ax-X)(by-Y) - (ay-Y)(bx-X), b_k = w_k / area.
+ *   Covered iff every b_k >= 0 and X, Y lie in the closed bounding box of the corners.  z = (b0 az + b1 bz) + b2 cz; a hit with !(z >= 0) is
+ *   dropped, -0 becomes +0.  Per pixel the smallest z wins, a tie goes to the smaller triangle index.
+ *   colour_c = (b0 ca + b1 cb) + b2 cc; render8 = trunc(clamp(colour, 0, 255)), NaN -> 0, 0 where uncovered.  D = z where covered, else -1.
+ *   Normal at an interior pixel, with p = (j dx, i dy, D), dx = -2 / W, dy = -2 / H: vw = p - p(i, j+1), vs = p(i+1, j) - p, ve = p - p(i, j-1),
+ *   vn = p(i-1, j) - p; n = N(N(vs x vw) + N(vn x ve)), N(u) = u / max(sqrt((ux ux + uy uy) + uz uz), 1e-8); a border pixel has (0,0,0).
+ *   normal8 = trunc((n + 1) 127.5), 0 where the pixel is uncovered or a render8 channel is 0.
+ *   Every operation is float32 and rounded on its own (no fused multiply-add), divisions and square roots correctly rounded.
+ * Outputs, each optional (NULL: not written), at least one given: face [B,3,H,W] int32 (-1: none); z [B,3,H,W] float32 = D;
+ *   normal [B,3,H,W,3] float32; render8, normal8 [B,3,H,W,3] uint8; cond [B,3,7,H,W] float32 = render8 / 255 (3), normal8 / 255 (3),
+ *   any(normal8 > 0).
+ * Workspaces the caller owns: keys [B,3,H,W] uint64 (bits(z) << 32 | triangle; all ones = uncovered), screen [B,3,V,4] float32, 16-byte aligned.
+ * Three launches on the stream: setup (screen, keys), cover (64-bit integer atomic min; a thread per triangle walks its pixel box, a box of
+ * more than hav_raster_param(2) pixels is walked by the whole wave), resolve (a workgroup per hav_raster_param(0) x hav_raster_param(1) pixel
+ * tile).  Every output element is written exactly once and nothing beyond; a minimum does not depend on arrival order: the same inputs give
+ * the same bits.  NULL inputs or workspaces, no output, a size < 1, a non-finite view34 entry, 3 B H W >= 2^31: HAV_EINVAL; more than
+ * 2^31 - 1 workgroups: HAV_EUNSUP; both before any launch.  No allocation, no synchronisation: capturable. */
+int hav_raster_param(int which);
+int hav_raster_ortho_f32(int32_t* face, float* z, float* normal, uint8_t* render8, uint8_t* normal8, float* cond, uint64_t* keys, float* screen,
+                         const float* verts, const float* colors, const int32_t* tris, int B, int V, int F, int H, int W, int colors_batched,
+                         const float* view34, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Trilinear x2 up-sampling of a [N,C,D,H,W] float32 volume and its adjoint -- nn.Upsample(scale_factor=2, mode='trilinear',
  * align_corners=False), the first stage of every UpConv3DBlock of the skinning-volume decoder
